@@ -1,6 +1,8 @@
 """bench.py -- pretraining throughput of the Point-DAE hot path on MI355X.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
+                                                                        #   (with ordered reductions: --deterministic)
     python bench.py --gpus N ...        # N > 1 without a launcher: starts the N ranks itself (child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -52,6 +54,11 @@ VALU_F32_PEAK_TOPS = 78.6         # fp32 vector peak counted WITHOUT fused multi
                                   # kernels are sub / mul / add / min chains
 EXP_PEAK_TOPS = 9.8               # v_exp_f32 per second (T/s): the transcendental rate VERDICT r3 prices EMD against
 ROUND = 6                         # profiles/*_rNN.json this bench refers to
+DUMP_BYTES = 60 * 10 ** 6         # --dump-outputs writes at most this much in all (within a 64 MB cap)
+# cpu_baseline_box: its workers never use the GPU, but each imports the ROCm build of torch, and on a 256-CPU host the 16
+# workers plus the benchmark were counted as 17 processes holding the GPU (hosts that cap that count stopped the run).  4 at
+# most keeps it at 5; `covers_whole_box` says when the figure is a part of the box
+CPU_BOX_MAX_PROCESSES = 4
 
 
 def parse():
@@ -79,7 +86,18 @@ def parse():
     p.add_argument('--no-calibration', action='store_true', help='skip the box calibration block and the three extra timed regions')
     p.add_argument('--no-tvis-table', action='store_true',
                    help='skip the per-visible-token-count replay timings and the straggler model built on them')
-    return p.parse_args()
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (dump_outputs); '
+                        'implies --deterministic')
+    p.add_argument('--deterministic', action='store_true',
+                   help='ordered reductions instead of float atomics (the library\'s deterministic mode): the same arguments '
+                        'compute the same steps bit for bit every run')
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    if args.dump_outputs:
+        args.deterministic = True
+    return args
 
 
 def _event_time_us(fn, iters=20, warm=3):
@@ -93,6 +111,35 @@ def _event_time_us(fn, iters=20, warm=3):
     e.record()
     torch.cuda.synchronize()
     return s.elapsed_time(e) / iters * 1e3
+
+
+def dump_outputs(path, out, model, grads=True):
+    """--dump-outputs DIR: what the timed path computed in its last step, as DIR/<name>.npy -- the two losses the step
+    returns (`loss`, `loss2`) and the model's flat parameter and gradient buffers as that step left them (`params`:
+    after its optimizer update; `grads`: the gradient it applied -- not written for the eager path, which clears it).  Buffers
+    too large for DUMP_BYTES in all are written as the same fixed sample in every run: the sorted element indices
+    numpy.random.default_rng(0) chooses, without replacement."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    arrays = {'loss': host(out[0]), 'loss2': host(out[1])}
+    flat = {'params': model.flat_param, 'grads': model.flat_grad} if grads else {'params': model.flat_param}
+    n = model.flat_param.numel()
+    room = DUMP_BYTES - sum(a.nbytes for a in arrays.values()) - 1024 * (len(arrays) + len(flat))   # (npy headers)
+    k = min(n, room // sum(8 if t.dtype == torch.float64 else 4 for t in flat.values()))
+    idx = None
+    if k < n:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, k, replace=False))).to(model.flat_param.device)
+    for name, t in flat.items():
+        arrays[name] = host(t if idx is None else t[idx])
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return {'dir': path, 'arrays': {name: {'shape': list(a.shape), 'dtype': str(a.dtype),
+                                           'sample_of': n if idx is not None and name in flat else None}
+                                    for name, a in arrays.items()}}
 
 
 def geometry_rooflines(args, clouds, shape=None):
@@ -694,9 +741,11 @@ def cpu_baseline(config, args):
 def cpu_baseline_box(args, one):
     """The same sample on the whole box: floor(logical CPUs / 16) processes, each pinned to 16 logical CPUs and running
     16 threads (the size at which ONE process is fastest: cpu_baseline), all at the same time; their rates summed.
+    At most CPU_BOX_MAX_PROCESSES of them: on a larger box the figure covers that many (`covers_whole_box` false).
     `one` = the single-process figure, kept as cpu_baseline.value."""
     import subprocess
-    n = (os.cpu_count() or 1) // 16
+    fit = (os.cpu_count() or 1) // 16
+    n = min(fit, CPU_BOX_MAX_PROCESSES)
     if n < 2:
         return None
     env = dict(os.environ, HIP_VISIBLE_DEVICES='', ROCR_VISIBLE_DEVICES='', OMP_NUM_THREADS='16')
@@ -714,6 +763,7 @@ def cpu_baseline_box(args, one):
     if not vals:
         return None
     return {'value': sum(vals), 'unit': 'clouds/s', 'processes': len(vals), 'threads_per_process': 16, 'cores': 16 * len(vals),
+            'covers_whole_box': len(vals) == fit,
             'per_process_min': min(vals), 'per_process_max': max(vals), 'kind': 'port',
             'sample': 'the cpu_baseline sample in %d processes at once, each pinned to 16 logical CPUs (of %d); rates summed; '
                       'one process alone on the idle box: %.1f clouds/s' % (len(vals), os.cpu_count(), one['value'])}
@@ -800,6 +850,13 @@ def main():
     if args.workload == 'cfg2':
         args.no_cpu_baseline = True         # the cpu_baseline leg times the cfg3 oracle model
     set_random_seed(0 + rank)
+    if args.deterministic:
+        # ordered reductions instead of float atomics (include/pdae.h: deterministic mode).  The atomics' order of arrival
+        # varies from run to run and AdamW amplifies that rounding step after step (the loss of two runs parts by ~1e-3
+        # within 30 steps), so outputs are comparable only in this mode; timing runs keep the default atomic path, the
+        # one training runs.  64 MiB of workspace covers the step at batch 128
+        from point_dae_amd import _lib
+        _lib.set_deterministic(True, 64 * max(1, -(-args.batch // 128)))
     model = FlatDataParallel(builder.model_builder(config.model).to(device))
     optimizer, _ = builder.build_opti_sche(model, config)
     model.train()
@@ -855,6 +912,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:       # before anything else runs a step: the last TIMED step's outputs
+        dumped = dump_outputs(args.dump_outputs, out, model, grads=not args.eager)
     # three more timed regions of 20 steps each (same bracketing; every rank runs them): their median next to the single
     # figure above, and the box calibration, so that a round-to-round delta can be told from box-to-box variance
     regions, calib = None, None
@@ -963,6 +1023,7 @@ def main():
                                    'full train step (fwd+loss+bwd+AdamW%s)' % ('+RCCL all-reduce' if world > 1 else ''),
                        'local_batch': args.batch, 'global_batch': args.batch * world, 'npoints': args.npoints,
                        'num_group': args.num_group, 'group_size': 32, 'parallelism': 'dp%d' % world, 'launch': 'eager' if args.eager else 'hipGraph replay',
+                       'reductions': 'ordered (deterministic mode)' if args.deterministic else 'float atomics',
                        'grad_allreduce': ('none (1 rank)' if world == 1 else
                                           'Transformer slice under the embedder backward (two graphs)' if getattr(step, 'split', False)
                                           else 'one flat all-reduce after the replay'),
@@ -980,6 +1041,8 @@ def main():
             # sanity of the timed steps: Chamfer loss of the first and of the last timed optimisation step
             'loss': {'first_timed_step': float(loss_first), 'last_timed_step': float(loss_last)},
         }
+        if dumped:
+            line['dump_outputs'] = dumped
         if per_tvis:
             # every dense FLOP of the step (row GEMMs, weight gradients, the embedder's fused convolutions) as the
             # EXPECTATION over P(T_vis) of the per-T_vis launch-site counts -- deterministic -- over the matching

@@ -8,6 +8,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# torch and MKL split CPU reductions by their thread count, which follows the host's core count unless set; the golden
+# fixtures' checksums and tolerances hold with the 8 threads they were made with (on a 256-CPU host the checkpoint-layout
+# checksum and two DGCNN fixtures failed without it).  The variables are read when torch loads, so this works because no
+# test module or plugin imports torch before this conftest; child processes inherit the setting
+CPU_THREADS = 8
+os.environ.setdefault('OMP_NUM_THREADS', str(CPU_THREADS))
+os.environ.setdefault('MKL_NUM_THREADS', str(CPU_THREADS))
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
@@ -28,6 +36,19 @@ def pytest_collection_modifyitems(config, items):
     for item in items:
         if "gpu" in item.keywords:
             item.add_marker(skip)
+
+
+_session_threads = []
+
+
+@pytest.fixture(autouse=True)
+def _same_cpu_threads():
+    """A test that sets torch's CPU thread count for itself does not pass it on to the tests after it."""
+    import torch
+    if not _session_threads:
+        _session_threads.append(torch.get_num_threads())
+    yield
+    torch.set_num_threads(_session_threads[0])
 
 
 @pytest.fixture(scope="session")

@@ -6,6 +6,7 @@ committed is data: inputs, the captured random draws, and the reference's
 outputs -- never reference source.
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_fixtures.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_fixtures.py droppath     # transformer_droppath_b2.npz only
 """
 import os
 import sys
@@ -212,7 +213,36 @@ def dgcnn_fixture(name, B, seed, corrupt_type=None):
     print(name, 'loss', loss.item(), 'size %.0f KB' % (os.path.getsize(path) / 1024))
 
 
+def droppath_fixture(name):
+    """The Transformer with stochastic depth ON (droppath_step.py): the reference's loss and gradient digests, computed
+    in droppath_step.PINNED_ENV, after checking that the oracle computes the same bits there."""
+    import json
+    import subprocess
+    from droppath_step import PINNED_ENV
+    env = dict(os.environ, **PINNED_ENV)
+    script = os.path.join(HERE, 'droppath_step.py')
+    from point_dae_amd.synthetic import shapenet_like_clouds
+    ref, orc = [json.loads(subprocess.run([sys.executable, script, side, '--new-input'], env=env, check=True,
+                                          capture_output=True, text=True).stdout.strip().splitlines()[-1])
+                for side in ('reference', 'oracle')]
+    assert ref == orc, 'the oracle does not reproduce the reference bit for bit'
+    names = sorted(ref['grads'])
+    path = os.path.join(HERE, name)
+    np.savez_compressed(path, pts=shapenet_like_clouds(2, 1024, seed=9), loss=np.float32(float.fromhex(ref['loss'])),
+                        names=np.array(names),
+                        grad_sha256=np.array([ref['grads'][n] for n in names]),
+                        grad_norm=np.array([ref['norms'][n] for n in names], dtype=np.float64),
+                        grad_sample=np.array([ref['samples'][n] + [0.0] * (256 - len(ref['samples'][n])) for n in names],
+                                             dtype=np.float32),
+                        grad_sample_len=np.array([len(ref['samples'][n]) for n in names], dtype=np.int64),
+                        cpu_vendor=np.array(str(ref['cpu_vendor'])))
+    print(name, 'loss', float.fromhex(ref['loss']), 'size %.0f KB' % (os.path.getsize(path) / 1024))
+
+
 if __name__ == '__main__':
+    if len(sys.argv) > 1 and sys.argv[1] == 'droppath':
+        droppath_fixture('transformer_droppath_b2.npz')
+        sys.exit(0)
     R.setup()
     R.cpu_cuda_noop()
     if len(sys.argv) > 1 and sys.argv[1] == 'dgcnn':

@@ -1,9 +1,8 @@
 """Import the reference's PYTHON model code in the dev container, with the native
 ops it needs replaced by the CPU oracle.
 
-Used only by tests/golden/make_fixtures.py (and the optional CPU test that
-re-checks the oracle model against the live reference when /root/reference is
-present).  Nothing here travels as reference source: the reference is imported
+Used only by the fixture generators (tests/golden/make_*.py, and
+droppath_step.py's `reference` side behind make_fixtures.py droppath).  Nothing here travels as reference source: the reference is imported
 from where it lies, read-only, with bytecode writing disabled.
 
 Recipe: stub the modules absent from this image

@@ -3,6 +3,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -60,3 +62,63 @@ def test_ddp_model_expected_maximum_matches_a_monte_carlo_draw():
         got = model['predicted'][str(n)]
         assert abs(got['expected_max_replay_ms'] - sim) < 5e-3, (n, got, sim)
         assert abs(got['speedup'] - n * (ms[:, 0].mean() + 0.4) / (sim + 0.4)) < 5e-3
+
+
+def test_steps_below_one_is_refused():
+    r = _run(['--steps', '0', '--warmup', '0'])
+    assert r.returncode != 0 and '--steps' in r.stderr
+    assert '{"metric"' not in r.stdout
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs DIR: the step's two losses and the flat parameter / gradient buffers as float32 .npy files, at most
+    64 MB in all; buffers too large for that are written as the same seeded sample of elements in every run."""
+    import importlib.util
+    import types
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 12 * 10 ** 6                                           # 2 x 48 MB as float32: over the budget
+    g = torch.Generator().manual_seed(0)
+    model = types.SimpleNamespace(flat_param=torch.randn(n, generator=g), flat_grad=torch.randn(n, generator=g))
+    out = (torch.tensor(0.25), torch.zeros(1))
+    recs = [bench.dump_outputs(str(tmp_path / d), out, model) for d in ('a', 'b')]
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['grads.npy', 'loss.npy', 'loss2.npy', 'params.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64 * 10 ** 6
+    assert recs[0]['arrays']['params']['sample_of'] == n and recs[0]['arrays']['loss']['sample_of'] is None
+    a = {f: np.load(tmp_path / 'a' / f) for f in files}
+    assert all(v.dtype == np.float32 for v in a.values()) and a['loss.npy'] == np.float32(0.25)
+    for f in files:
+        assert np.array_equal(a[f], np.load(tmp_path / 'b' / f)), f
+    k = a['params.npy'].size
+    idx = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    assert np.array_equal(a['params.npy'], model.flat_param.numpy()[idx])
+    assert np.array_equal(a['grads.npy'], model.flat_grad.numpy()[idx])
+    small = types.SimpleNamespace(flat_param=torch.arange(10.), flat_grad=torch.ones(10))
+    bench.dump_outputs(str(tmp_path / 'c'), out, small)                  # within the budget: whole buffers
+    assert np.array_equal(np.load(tmp_path / 'c' / 'params.npy'), np.arange(10, dtype=np.float32))
+    bench.dump_outputs(str(tmp_path / 'd'), out, small, grads=False)     # the eager path: its gradient is cleared
+    assert sorted(os.listdir(tmp_path / 'd')) == ['loss.npy', 'loss2.npy', 'params.npy']
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_every_run(tmp_path):
+    """Two runs of bench.py with the same arguments compute the same last timed step, bit for bit: the inputs are seeded
+    and --dump-outputs runs the step with ordered reductions (--deterministic)."""
+    import numpy as np
+    import proc_util
+    args = ['--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '16', '--no-also', '--no-cpu-baseline',
+            '--no-calibration', '--no-tvis-table', '--probe-steps', '0']
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'PDAE_BENCH_BACKEND')}
+    for d in ('a', 'b'):
+        r = proc_util.run([sys.executable, os.path.join(ROOT, 'bench.py')] + args + ['--dump-outputs', str(tmp_path / d)],
+                          timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-4000:]
+        assert '"ms_per_step"' in r.stdout
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['grads.npy', 'loss.npy', 'loss2.npy', 'params.npy']
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)), f
