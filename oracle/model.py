@@ -477,6 +477,13 @@ class _SharedMLP(nn.Sequential):
             self.add_module('layer{}'.format(i), _ConvBN(spec[i], spec[i + 1]))
 
 
+# Parity-test hook (empty by default: the reference's max_pool2d).  A list of (B, C, npoint) int64 winner indices into
+# the nsample axis, consumed one entry per set-abstraction level in forward order: that level then pools by gathering
+# its pre-pool activations at the given winners, and the backward routes the gradient through them -- the product's
+# own winners replayed on this side (tests/test_gpu_model.py).
+POOL_AT = []
+
+
 class SAModule(nn.Module):
     def __init__(self, mlp, npoint=None, radius=None, nsample=None):
         super().__init__()
@@ -498,7 +505,10 @@ class SAModule(nn.Module):
             if features is not None:
                 grouped = torch.cat([grouped, features.unsqueeze(2)], dim=1)
         f = self.mlps[0](grouped)
-        f = F.max_pool2d(f, kernel_size=[1, f.size(3)]).squeeze(-1)
+        if POOL_AT:                                    # (parity tests) pool at the given winners, one level per entry
+            f = f.gather(3, POOL_AT.pop(0).unsqueeze(-1)).squeeze(-1)
+        else:
+            f = F.max_pool2d(f, kernel_size=[1, f.size(3)]).squeeze(-1)
         return new_xyz, f
 
 

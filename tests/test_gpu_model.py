@@ -103,42 +103,32 @@ def test_cfg3_full_batch_step_runs_and_learns():
     assert losses[-1] < losses[0], losses
 
 
-@pytest.mark.parametrize('name', ['PointCAE_transformer', 'PointCAE_transformer_fc_global_folding_local'])
-def test_cfg3_full_batch_loss_and_gradients_equal_the_oracle(name):
-    """BASELINE cfg3 (and the published runs' model on the same YAML) at FULL size (B=128, N=1024, G=64, k=32, depth 12 / 4, random mask + affine_r3 draws): loss of the
-    HIP model == the CPU oracle model's on the same weights and host RNG draws (1e-5), and the gradients agree in
-    relative L2 norm tensor by tensor (the batch is large enough that BatchNorm's statistics and every reduction order
-    differ between the two sides: a size-dependent bug -- a tile edge, a split-K slab, a 32-bit offset -- shows here and
-    not in the B=2 fixtures)."""
-    import os
+def _transformer_loss_and_gradients_against_the_oracle(config, name, B, N, wseed, xseed, rseed):
+    """Loss, second loss and every gradient of the HIP model against the CPU oracle model on the same weights
+    (fill_state), clouds and host RNG draws (mask, affine maps): both losses within 1e-5, every gradient tensor compared
+    in relative L2 norm -> (worst relative error, tensor, |oracle grad|, |HIP grad|).  The three conv biases whose effect
+    a later BatchNorm cancels have a TRUE gradient of zero: rounding residue on the oracle's side, residue or exactly
+    zero here -- both norms within 1e-4 of the largest gradient's."""
     import random
     from oracle import model as OM
-    from point_dae_amd.config import cfg_from_yaml_file
-    from point_dae_amd.point_cae_transformer import PointCAE_transformer
-    from point_dae_amd.synthetic import shapenet_like_clouds
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    config = cfg_from_yaml_file(os.path.join(
-        root, 'cfgs', 'pretrain_PointCAE_transformer_dropout_patch_affine_r3_maskpatch_p0005_whole.yaml'))
-    config.model.transformer_config.drop_path_rate = 0.0
     from point_dae_amd import point_cae_transformer as PM
-    ref = fill_state(getattr(OM, name)(config.model), 5).train()
-    mine = fill_state(getattr(PM, name)(config.model), 5).cuda().train()
-    x = shapenet_like_clouds(128, 1024, seed=3)
+    from point_dae_amd.synthetic import shapenet_like_clouds
+    ref = fill_state(getattr(OM, name)(config.model), wseed).train()
+    mine = fill_state(getattr(PM, name)(config.model), wseed).cuda().train()
+    x = shapenet_like_clouds(B, N, seed=xseed)
 
     def seed(s):
         random.seed(s), np.random.seed(s), torch.manual_seed(s)
-    seed(91)
+    seed(rseed)
     l_ref, l2_ref = ref(torch.from_numpy(x), torch.from_numpy(x))
     (l_ref + l2_ref.sum()).backward()
-    seed(91)
+    seed(rseed)
     l_my, l2_my = mine(torch.from_numpy(x).cuda(), torch.from_numpy(x).cuda())
     (l_my + l2_my.sum()).backward()
     assert abs(l_my.item() - l_ref.item()) <= 1e-5 * abs(l_ref.item()), (l_my.item(), l_ref.item())
     assert abs(l2_my.sum().item() - l2_ref.sum().item()) <= 1e-5 * abs(l2_ref.sum().item()) + 1e-12
     gref = {n: p for n, p in ref.named_parameters() if p.grad is not None}
     top = max(p.grad.norm().item() for p in gref.values())
-    # the three conv biases whose effect a later BatchNorm cancels have a TRUE gradient of zero: rounding residue on the
-    # oracle's side, residue or exactly zero (INTEGRATION.md 4) here
     dead = ('encoder.first_conv.0.bias', 'encoder.first_conv.3.bias', 'encoder.second_conv.0.bias')
     worst = (0.0, None)
     for n, p in mine.named_parameters():
@@ -151,6 +141,24 @@ def test_cfg3_full_batch_loss_and_gradients_equal_the_oracle(name):
             continue
         rel = (g - r).norm().item() / max(r.norm().item(), 1e-6 * top)
         worst = max(worst, (rel, n, r.norm().item(), g.norm().item()))
+    print(name, 'B=%d N=%d G=%d: worst gradient' % (B, N, config.model.num_group), worst)
+    return worst
+
+
+@pytest.mark.parametrize('name', ['PointCAE_transformer', 'PointCAE_transformer_fc_global_folding_local'])
+def test_cfg3_full_batch_loss_and_gradients_equal_the_oracle(name):
+    """BASELINE cfg3 (and the published runs' model on the same YAML) at FULL size (B=128, N=1024, G=64, k=32, depth 12 / 4, random mask + affine_r3 draws): loss of the
+    HIP model == the CPU oracle model's on the same weights and host RNG draws (1e-5), and the gradients agree in
+    relative L2 norm tensor by tensor (the batch is large enough that BatchNorm's statistics and every reduction order
+    differ between the two sides: a size-dependent bug -- a tile edge, a split-K slab, a 32-bit offset -- shows here and
+    not in the B=2 fixtures)."""
+    import os
+    from point_dae_amd.config import cfg_from_yaml_file
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    config = cfg_from_yaml_file(os.path.join(
+        root, 'cfgs', 'pretrain_PointCAE_transformer_dropout_patch_affine_r3_maskpatch_p0005_whole.yaml'))
+    config.model.transformer_config.drop_path_rate = 0.0
+    worst = _transformer_loss_and_gradients_against_the_oracle(config, name, 128, 1024, 5, 3, 91)
     assert worst[0] <= 1e-3, worst                     # (measured 2.1e-4: the embedder's first BatchNorm bias)
 
 
@@ -399,6 +407,123 @@ def test_cfg2_mid_batch_gradients_equal_the_oracle():
         assert rel <= 5e-3, (n, rel)
 
 
+def test_cfg2_full_batch_losses_equal_the_oracle():
+    """BASELINE config 2 at its own batch (B=128, N=1024: 2.1 M folding rows, 65 k first-level set-abstraction groups):
+    both Chamfer losses of one training-mode forward equal the CPU oracle model's (oracle/model.py, bit-equal to the
+    live reference) to 1e-5 on the same weights and the clouds the six-step run trains on."""
+    import os
+    import sys
+    from oracle import model as OM
+    from point_dae_amd import builder
+    from point_dae_amd.config import cfg_from_yaml_file
+    from point_dae_amd.synthetic import shapenet_like_clouds
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, 'tests', 'golden'))
+    from weights import fill_state as fill
+    config = cfg_from_yaml_file(os.path.join(root, 'cfgs', 'pretrain_PointCAE_affine_r3_dropout_local_4xlonger.yaml'))
+    clean = shapenet_like_clouds(128, 1024, seed=1)
+    corrupted = shapenet_like_clouds(128, 1024, seed=2)
+    torch.set_num_threads(min(os.cpu_count() or 1, 32))
+    orc = fill(OM.Point_CAE_PointNetv2(config.model), 17).train()
+    with torch.no_grad():
+        o1, o2 = orc(torch.from_numpy(corrupted), torch.from_numpy(clean))
+    mine = fill(builder.model_builder(config.model), 17).cuda().train()
+    m1, m2 = mine(torch.from_numpy(corrupted).cuda(), torch.from_numpy(clean).cuda())
+    print('cfg2 B=128 losses', (m1.item(), o1.item()), (m2.item(), o2.item()))
+    for got, ref, name in ((m1, o1, 'coarse'), (m2, o2, 'fine')):
+        assert abs(got.item() - ref.item()) <= 1e-5 * abs(ref.item()), (name, got.item(), ref.item())
+
+
+def _oracle_layout(arg, B):
+    """(B * npoint, C) uint8 winners of a HIP set-abstraction max-pool -> the oracle's (B, C, npoint) int64 indices."""
+    return arg.long().cpu().view(B, -1, arg.shape[1]).permute(0, 2, 1).contiguous()
+
+
+def test_cfg2_mid_batch_gradients_on_the_products_own_winners():
+    """BASELINE config 2 at B=32 (N=1024) the other way round from the test above: the HIP model runs the product's
+    path end to end -- default mode, its OWN max-pool winners (sa_mlp.ARG_HOOK only observes them) -- and the CPU oracle
+    model is made to pool at those winners (oracle/model.py POOL_AT).  (a) Every winner that differs from the oracle's
+    own argmax is a near-tie in the oracle's un-injected pre-pool activations: max - f[winner] within a small fraction
+    of that channel's largest |f| over the batch.  (b) The injected oracle's losses equal the un-injected oracle's (and
+    the HIP model's) to 1e-5.  (c) Every HIP gradient tensor is within 5e-3 relative L2 of the injected oracle's."""
+    import os
+    import sys
+    from oracle import model as OM
+    from point_dae_amd import builder, sa_mlp
+    from point_dae_amd.config import cfg_from_yaml_file
+    from point_dae_amd.synthetic import shapenet_like_clouds
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, 'tests', 'golden'))
+    from weights import fill_state as fill
+    config = cfg_from_yaml_file(os.path.join(root, 'cfgs', 'pretrain_PointCAE_affine_r3_dropout_local_4xlonger.yaml'))
+    B = 32
+    clean = shapenet_like_clouds(B, 1024, seed=81)
+    corrupted = shapenet_like_clouds(B, 1024, seed=82)
+    torch.set_num_threads(min(os.cpu_count() or 1, 32))
+    orc = fill(OM.Point_CAE_PointNetv2(config.model), 23).train()
+    pre = {}
+    enc = orc.pointnetv2_encoder
+    for lvl, sa in enumerate((enc.sa1, enc.sa2, enc.sa3)):
+        sa.mlps[0].register_forward_hook(lambda m, i, o, lvl=lvl: pre.update({lvl: o.detach()}))   # (B, C, npoint, ns)
+    with torch.no_grad():
+        o1, o2 = orc(torch.from_numpy(corrupted), torch.from_numpy(clean))
+    f = [pre[lvl] for lvl in range(3)]
+
+    mine = fill(builder.model_builder(config.model), 23).cuda().train()
+    seen = []
+
+    def observe(arg):
+        seen.append(arg.clone())
+        return arg
+    sa_mlp.ARG_HOOK = observe
+    try:
+        m1, m2 = mine(torch.from_numpy(corrupted).cuda(), torch.from_numpy(clean).cuda())
+        (m1 + 0.5 * m2).backward()
+    finally:
+        sa_mlp.ARG_HOOK = None
+    assert len(seen) == 3
+    winners = [_oracle_layout(a, B) for a in seen]
+
+    # (a) the winners the product chose differently are near-ties on the oracle's side
+    flips, gaps = [], []
+    for lvl in range(3):
+        assert winners[lvl].shape == f[lvl].shape[:3], (lvl, winners[lvl].shape, f[lvl].shape)
+        assert int(winners[lvl].max()) < f[lvl].shape[3]
+        at = f[lvl].gather(3, winners[lvl].unsqueeze(-1)).squeeze(-1)
+        top = f[lvl].amax(3)
+        scale = f[lvl].abs().amax(dim=(0, 2, 3)).clamp_min(1e-30).view(1, -1, 1)
+        gap = ((top - at) / scale).max().item()                  # 0 wherever the winner holds the maximum value
+        flips.append((int((winners[lvl] != f[lvl].argmax(3)).sum()), int((at != top).sum())))
+        gaps.append(gap)
+    print('cfg2 B=32 own winners: flips per level (index differs, value differs)', flips, 'worst gap / channel max',
+          gaps)
+    assert max(gaps) <= 1e-5, (flips, gaps)              # (measured 5.1e-7: GEMM and BatchNorm rounding, not a wrong row)
+
+    # (b) the injected oracle computes the same losses
+    OM.POOL_AT[:] = winners
+    try:
+        i1, i2 = orc(torch.from_numpy(corrupted), torch.from_numpy(clean))
+        assert not OM.POOL_AT                                     # every level consumed its winners
+    finally:
+        OM.POOL_AT.clear()
+    (i1 + 0.5 * i2).backward()
+    for inj, ref, got, name in ((i1, o1, m1, 'coarse'), (i2, o2, m2, 'fine')):
+        assert abs(inj.item() - ref.item()) <= 1e-5 * abs(ref.item()), (name, inj.item(), ref.item())
+        assert abs(got.item() - ref.item()) <= 1e-5 * abs(ref.item()), (name, got.item(), ref.item())
+
+    # (c) every gradient, no named exceptions
+    rels = []
+    for (n, p), (nm, q) in zip(orc.named_parameters(), mine.named_parameters()):
+        assert n == nm, (n, nm)
+        if p.grad is None:
+            continue
+        rel = ((q.grad.cpu().double() - p.grad.double()).norm() / p.grad.double().norm().clamp_min(1e-30)).item()
+        rels.append((rel, n))
+    print('cfg2 B=32 own winners: worst gradient tensors', sorted(rels, reverse=True)[:5])
+    for rel, n in rels:
+        assert rel <= 5e-3, (n, rel)
+
+
 def test_cfg5_shape_runs():
     """BASELINE config 5 shape: N=2048, G=128, k=32 (decoder T=128, T_vis up to 64)."""
     import os
@@ -465,6 +590,26 @@ def test_cfg5_full_depth_step_against_oracle_loss():
     losses = [step(x)[0].item() for _ in range(8)]
     assert len(step.graphs) >= 1
     assert all(np.isfinite(losses)) and min(losses[-3:]) < losses[0], losses
+
+
+def test_cfg5_per_gpu_batch_loss_and_gradients_equal_the_oracle():
+    """BASELINE config 5's per-GPU shape at its own batch (N=2048, G=128, k=32, encoder 12 / decoder 4, B=32: 131 k
+    embedder rows, decoder attention over T=128 tokens, 26..64 visible tokens, kNN over 2048 points): loss and second
+    loss of the HIP model == the CPU oracle model's on the same weights and host RNG draws (1e-5), every gradient
+    within 1e-3 in relative L2 -- the shape with the project's largest row counts, where a size-dependent bug (a tile
+    edge, a split-K slab, a 32-bit offset, the T > 64 attention path) would show and nowhere else."""
+    import os
+    from point_dae_amd.config import cfg_from_yaml_file
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    config = cfg_from_yaml_file(os.path.join(
+        root, 'cfgs', 'pretrain_PointCAE_transformer_dropout_patch_affine_r3_maskpatch_p0005_double.yaml'))
+    config.npoints = 2048
+    config.model.num_group = 128
+    assert config.model.transformer_config.depth == 12 and config.model.transformer_config.decoder_depth == 4
+    config.model.transformer_config.drop_path_rate = 0.0
+    torch.set_num_threads(min(os.cpu_count() or 1, 32))
+    worst = _transformer_loss_and_gradients_against_the_oracle(config, 'PointCAE_transformer', 32, 2048, 13, 33, 79)
+    assert worst[0] <= 1e-3, worst
 
 
 @pytest.mark.parametrize('group_size,num_group', [(16, 64), (64, 32)])

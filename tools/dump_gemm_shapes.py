@@ -1,11 +1,15 @@
 """Every distinct product the row-GEMM family computes in one optimisation step of cfg3 (PointCAE_transformer, B = 128,
-all visible-token counts the mask ratio can draw), the published variant and cfg2 (Point_CAE_PointNetv2, B = 128):
-recorded at the C boundary (point_dae_amd/_lib.CALL_HOOK) while the steps run eagerly -> tests/golden/gemm_shapes.json,
-the shape list of tests/test_gpu_rows3.py.    gpurun -- python tools/dump_gemm_shapes.py"""
+all visible-token counts the mask ratio can draw), the published variant, cfg2 (Point_CAE_PointNetv2, B = 128), the cfg5
+per-GPU shape (N = 2048, G = 128, B = 32: 20 drawn visible-token counts and both ends, 26 and 64) and DGCNN
+(Point_CAE_DGCNN_FCOnly on the cfg2 YAML, B = 32): recorded at the C boundary (point_dae_amd/_lib.CALL_HOOK) while the
+steps run eagerly -> tests/golden/gemm_shapes.json, the shape list of tests/test_gpu_rows3.py.  Run on a GPU:
+python tools/dump_gemm_shapes.py"""
 import json
 import os
+import random
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,6 +23,8 @@ gemm, wgrad = set(), set()
 def hook(name, a):
     if name == 'pdae_rows_gemm':
         gemm.add((a[0], a[1], a[2], int(a[5]), int(a[7])))          # M, N, K, w_kn, epi
+    elif name == 'pdae_rows_gemm_bnrelu_stats':                       # a data gradient into relu(bn(X)), [K, N] weight,
+        gemm.add((a[0], a[1], a[2], 1, 5, int(a[6] is not None)))    # BatchNorm-backward's sums: epi 5, X listed or not
     elif name == 'pdae_rows_wgrad_listed':
         wgrad.add((a[0], a[1], a[2], int(a[4] is not None), int(a[6] is not None), int(a[7] is not None)))
     elif name == 'pdae_rows_wgrad_multi':
@@ -38,20 +44,26 @@ def main():
     device = torch.device('cuda', 0)
     use_created_stream(device)
     out = {}
-    B, N = 128, 1024
-    x = torch.from_numpy(shapenet_like_clouds(2 * B, N, seed=7)).to(device)
-    for wl in ('cfg3', 'published', 'cfg2'):
+    for wl in ('cfg3', 'published', 'cfg2', 'cfg5', 'dgcnn'):
         gemm.clear(), wgrad.clear()
-        config = cfg_from_yaml_file(os.path.join(ROOT, bench.CFG2 if wl == 'cfg2' else bench.CFG3))
+        B, N = (32, 2048) if wl == 'cfg5' else ((32, 1024) if wl == 'dgcnn' else (128, 1024))
+        x = torch.from_numpy(shapenet_like_clouds(2 * B, N, seed=7)).to(device)
+        config = cfg_from_yaml_file(os.path.join(ROOT, {'cfg2': bench.CFG2, 'dgcnn': bench.CFG2,
+                                                        'cfg5': bench.CFG5}.get(wl, bench.CFG3)))
         if wl == 'published':
             config.model.NAME = 'PointCAE_transformer_fc_global_folding_local'
+        elif wl == 'dgcnn':
+            config.model.NAME = 'Point_CAE_DGCNN_FCOnly'
+        elif wl == 'cfg5':
+            config.npoints, config.model.num_group = N, 128
+            random.seed(5), np.random.seed(5), torch.manual_seed(5)       # (39 counts can be drawn: a fixed 20)
         model = FlatDataParallel(builder.model_builder(config.model).to(device), broadcast=False, process_group=None)
         model.world_size = 1
         optimizer, _ = builder.build_opti_sche(model, config)
         model.train()
         model.zero_grad()
         _lib.CALL_HOOK = hook
-        if wl == 'cfg2':
+        if wl in ('cfg2', 'dgcnn'):
             step = GraphedStaticStep(model, optimizer, lambda a, b: a + 0.5 * b, B, N)
             step(x[:B], x[B:])                    # the first calls of a graphed step run eagerly
         else:
@@ -67,6 +79,15 @@ def main():
                 model.zero_grad()
                 if len(seen) == 20:
                     break
+            if wl == 'cfg5':
+                G = config.model.num_group
+                for tvis in (G - int(0.8 * G), G - int(0.5 * G)):     # the two ends of the mask ratio's range
+                    if tvis not in seen:
+                        step.pts.copy_(x[:B])
+                        seen.add(step._draw(tvis))
+                        step._fwd_bwd(tvis)
+                        model.zero_grad()
+                print(wl, 'visible-token counts', sorted(seen), flush=True)
         _lib.CALL_HOOK = None
         torch.cuda.synchronize()
         out[wl] = {'gemm': sorted(gemm), 'wgrad': sorted(wgrad)}
