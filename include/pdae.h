@@ -919,6 +919,63 @@ int pdae_adamw_step(long long n, float* param, const float* grad,
                     float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int step,
                     pdae_stream_t stream);
+/* adamw_step_gscale: pdae_adamw_step reading g * (*gscale) in place of g (the
+ * multiply first, as torch scales .grad before the optimiser reads it); gscale
+ * is a device scalar, e.g. grad_norm_clip's coefficient. */
+int pdae_adamw_step_gscale(long long n, float* param, const float* grad,
+                           float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, int step,
+                           const float* gscale, pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Classification fine-tuning glue (csrc/finetune.hip; models/Point_MAE.py:578-706
+ * PointTransformer, tools/runner_finetune.py:81-270).  Every reduction runs in a
+ * fixed order (no float atomics).
+ *   prepend_token       out (B, 1+G, C) = per cloud [token (C) | x (B, G, C)];
+ *                       _grad: dx (B, G, C) = dout[:, 1:], dtoken (C) = sum over b
+ *                       (ascending) of dout[b, 0].  C % 4 == 0, buffers 16-byte
+ *                       aligned.
+ *   cls_max_concat      out (B, 2C) = [x[:, 0] | max_{t>=1} x[:, t]] of x (B, T, C),
+ *                       arg (B, C) uint8 = the first maximal t (2 <= T <= 256);
+ *                       _grad: dx (B, T, C) dense.  For finite x: a NaN is passed
+ *                       over, where torch.max would return NaN.
+ *   bn_relu_dropout     out = Dropout(p)(ReLU(BatchNorm1d(y))) of y (B, N).
+ *                       training != 0: batch mean / biased variance (fp64) normalise,
+ *                       running_mean / running_var (unbiased, momentum; nullable)
+ *                       and num_batches_tracked (nullable) are updated, mean and
+ *                       invstd (N) are written for the backward; an element is kept
+ *                       when u (B, N uniforms; NULL = no dropout) >= p and scaled by
+ *                       1/(1-p).  training == 0: the running estimates, no dropout.
+ *                       _grad (training mode): dy, dgamma, dbeta in one launch.
+ *   softmax_xent        nn.CrossEntropyLoss() (mean, no smoothing) of logits (B, K)
+ *                       against int64 labels in [0, K): *loss, *correct = the count of
+ *                       rows whose first maximal logit is the label (float).  K <= 64,
+ *                       B <= 4096.  A label outside [0, K) makes the loss NaN.
+ *                       _grad: dlogits = (softmax - onehot) * (*dloss) / B.
+ *   grad_norm_clip      the L2 norm of grad (n floats, 16-byte aligned) as
+ *                       grad_norm_parts(n) fp64 per-block partials (caller's
+ *                       workspace) added in block order: *norm (nullable) and *coef =
+ *                       min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_), on the
+ *                       device.                                                    */
+int pdae_prepend_token(int B, int G, int C, const float* x, const float* token, float* out, pdae_stream_t stream);
+int pdae_prepend_token_grad(int B, int G, int C, const float* dout, float* dx, float* dtoken, pdae_stream_t stream);
+int pdae_cls_max_concat(int B, int T, int C, const float* x, float* out, unsigned char* arg, pdae_stream_t stream);
+int pdae_cls_max_concat_grad(int B, int T, int C, const float* dout, const unsigned char* arg, float* dx,
+                             pdae_stream_t stream);
+int pdae_bn_relu_dropout(int B, int N, const float* y, const float* gamma, const float* beta, float eps,
+                         float momentum, float* running_mean /*nullable*/, float* running_var /*nullable*/,
+                         long long* num_batches_tracked /*nullable*/, int training, float p,
+                         const float* u /*nullable*/, float* out, float* mean, float* invstd, pdae_stream_t stream);
+int pdae_bn_relu_dropout_grad(int B, int N, const float* y, const float* gamma, const float* beta, const float* mean,
+                              const float* invstd, float p, const float* u /*nullable*/, const float* dout, float* dy,
+                              float* dgamma, float* dbeta, pdae_stream_t stream);
+int pdae_softmax_xent(int B, int K, const float* logits, const int64_t* labels, float* loss, float* correct,
+                      pdae_stream_t stream);
+int pdae_softmax_xent_grad(int B, int K, const float* logits, const int64_t* labels, const float* dloss,
+                           float* dlogits, pdae_stream_t stream);
+int pdae_grad_norm_parts(long long n);
+int pdae_grad_norm_clip(long long n, const float* grad, float max_norm, double* partials, float* norm /*nullable*/,
+                        float* coef, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Measurement aids: box calibration for bench.py (csrc/calib.hip).  They replace nothing of the reference; the training

@@ -127,6 +127,16 @@ _SIGNATURES = {
     "pdae_embed_split_conv3_weight": [_i, _i, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_masked_prep": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_dw3_assemble": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_adamw_step_gscale": [ctypes.c_longlong, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp, _vp],
+    "pdae_prepend_token": [_i, _i, _i, _vp, _vp, _vp, _vp],
+    "pdae_prepend_token_grad": [_i, _i, _i, _vp, _vp, _vp, _vp],
+    "pdae_cls_max_concat": [_i, _i, _i, _vp, _vp, _vp, _vp],
+    "pdae_cls_max_concat_grad": [_i, _i, _i, _vp, _vp, _vp, _vp],
+    "pdae_bn_relu_dropout": [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "pdae_bn_relu_dropout_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_softmax_xent": [_i, _i, _vp, _vp, _vp, _vp, _vp],
+    "pdae_softmax_xent_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp],
+    "pdae_grad_norm_clip": [ctypes.c_longlong, _vp, _f, _vp, _vp, _vp, _vp],
     "pdae_calib_mfma_bf16": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_calib_copy": [ctypes.c_longlong, _vp, _vp, _vp],
 }
@@ -152,6 +162,7 @@ _HOST = {
     "pdae_ctx_current": [],
     "pdae_cloud_pool_splits": [_i, _i],
     "pdae_rows_gemm_bnrelu_stats_workspace": [_i, _i],
+    "pdae_grad_norm_parts": [ctypes.c_longlong],
 }
 _STR = ("pdae_version", "pdae_last_error")
 

@@ -515,17 +515,47 @@ class ModelNet:
         self.subset = config.get('subset', 'test')
         self.device = config.get('device', 'cuda')
         seed = config.get('seed', 0) + (1000 if self.subset == 'train' else 2000)
-        x, y = labelled_clouds(self.count, self.npoints, seed=seed, classes=min(3, config.get('NUM_CATEGORY', 3)))
+        # `classes`: how many of the NUM_CATEGORY labels the synthetic clouds use (default 3)
+        classes = int(config.get('classes', min(3, config.get('NUM_CATEGORY', 3))))
+        x, y = labelled_clouds(self.count, self.npoints, seed=seed, classes=classes)
         rank, world = int(config.get('rank', 0)), max(int(config.get('world', 1)), 1)
         if world > 1:      # DistributedSampler(shuffle=False): wrap-padded to a multiple of world, every world-th item
             sel = np.resize(np.arange(self.count), -(-self.count // world) * world)[rank::world]
             x, y = x[sel], y[sel]
             self.count = len(sel)
         self.x, self.y = torch.from_numpy(x).to(self.device), torch.from_numpy(y).to(self.device)
+        # augment_data (corrupt_util.py:1155-1175) of every batch, in the configured order, as ModelNetDataset does for the
+        # fine-tuning configs ('norm', 'scale', 'translate'); 'clean' (the probe configs) and no key leave the clouds as they are
+        self.aug_type = [a for a in config.get('aug_type', ['clean']) if a != 'clean']
+        for item in self.aug_type:
+            if item not in _AUGS:
+                raise NotImplementedError('augmentation %r (implemented: %s)' % (item, ', '.join(_AUGS)))
+        self.rng = np.random.default_rng(seed + 17) if self.aug_type else None
 
     def __len__(self):
         return (self.count + self.bs - 1) // self.bs
 
+    def augment(self, x):
+        """augment_data of one batch on csrc/pipeline.hip: a 'norm' normalises everything drawn before it first (the kernel
+        normalises before it applies its <= 3 maps), every other item is one affine map per cloud."""
+        B = x.shape[0]
+        maps, norm_pending = [[] for _ in range(B)], False
+
+        def flush(x, norm_pending, maps):
+            while norm_pending or any(maps):
+                x = pipeline_norm_affine(x, norm_pending, [m[:3] for m in maps] if any(maps) else None)
+                maps, norm_pending = [m[3:] for m in maps], False
+            return x
+        for item in self.aug_type:
+            if item == 'norm':
+                x = flush(x, norm_pending, maps)
+                maps, norm_pending = [[] for _ in range(B)], True
+                continue
+            for b in range(B):
+                maps[b].append(draw_affine_map(self.rng, 'aug_' + item))
+        return flush(x, norm_pending, maps)
+
     def __iter__(self):
         for i in range(0, self.count, self.bs):
-            yield 'ModelNet', i, (self.x[i:i + self.bs], self.y[i:i + self.bs])
+            x = self.x[i:i + self.bs]
+            yield 'ModelNet', i, (self.augment(x) if self.aug_type else x, self.y[i:i + self.bs])

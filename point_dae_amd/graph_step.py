@@ -514,3 +514,67 @@ class GraphedStaticStep:
             _average_gradients(self.model)
         self.optimizer.step()
         return out
+
+
+class GraphedClassifierStep:
+    """The fine-tuning step of the classifier (runner_finetune.py, point_transformer.PointTransformer): forward,
+    cross-entropy, backward and -- on one process -- the gradient-norm clip coefficient captured as ONE graph, replayed
+    every step.  It takes the resampled (points, labels) of a batch (the FPS + host subset draw + gather run in front
+    of it).  The head's dropout and the blocks' stochastic depth draw from torch's device generator inside the graph, so
+    every replay draws afresh.  AdamW stays outside the graph (its lr is a host argument), reading the coefficient on
+    the device; with several processes the all-reduce and then the coefficient run between the replay and AdamW (the
+    norm of the averaged gradient, as DistributedDataParallel + clip_grad_norm_)."""
+
+    def __init__(self, model, optimizer, clip, batch_size, npoints, warmup_eager=2):
+        assert isinstance(model, FlatDataParallel)
+        self.model, self.optimizer, self.clip = model, optimizer, clip
+        dev = model.flat_param.device
+        self.points = torch.zeros(batch_size, npoints, 3, device=dev)
+        self.labels = torch.zeros(batch_size, dtype=torch.int64, device=dev)
+        self.graph, self.out = None, None
+        _warn_if_null_stream()
+        self.eager_left = warmup_eager
+
+    def invalidate(self):
+        self.graph, self.out = None, None
+
+    def _fwd_bwd(self):
+        m = self.model
+        for p in m.params:
+            p.grad = None
+        ret = m(self.points)
+        loss, acc = m.module.get_loss_acc(ret, self.labels)
+        loss.backward()
+        _copy_into_views([(v, p.grad) for p, v in zip(m.params, m.grad_views)])
+        for p, v in zip(m.params, m.grad_views):
+            p.grad = v
+        coef = self.clip() if self.clip is not None and m.world_size == 1 else None
+        return loss.detach(), acc.detach(), coef
+
+    def __call__(self, points, labels):
+        self.points.copy_(points[:, :, :3], non_blocking=True)
+        self.labels.copy_(labels, non_blocking=True)
+        sync = self.model.require_sync
+        self.model.require_sync = False
+        if self.eager_left > 0:
+            self.eager_left -= 1
+            out = self._fwd_bwd()
+        else:
+            if self.graph is None:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side), _KeepBNState(self.model.module):
+                    self._fwd_bwd()
+                torch.cuda.current_stream().wait_stream(side)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
+                    self.out = self._fwd_bwd()
+            self.graph.replay()
+            out = self.out
+        self.model.require_sync = sync
+        loss, acc, coef = out
+        if self.model.world_size > 1:
+            _average_gradients(self.model)
+            coef = self.clip() if self.clip is not None else None
+        self.optimizer.step(grad_scale=coef)
+        return loss, acc

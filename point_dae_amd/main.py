@@ -1,11 +1,12 @@
 """Entry point: `python -m point_dae_amd.main --config cfgs/X.yaml [--launcher pytorch]`
-(main.py:16-111 of the reference, pretraining dispatch only)."""
+(main.py:16-111 of the reference): pretraining, or with --finetune_model / --scratch_model the
+classification fine-tuning runner."""
 import torch
 
 from . import dist_utils, parser
 from .config import get_config
 from .misc import set_random_seed
-from .runner_pretrain import run_net
+from . import runner_finetune, runner_pretrain
 
 
 def main(argv=None):
@@ -29,12 +30,16 @@ def main(argv=None):
         config.total_bs = args.total_bs
     if args.max_epoch != -1:
         config.max_epoch = args.max_epoch
-    if len(config.model['corrupt_type']) == 0:          # main.py:51-55
+    finetune = args.finetune_model or args.scratch_model
+    if not finetune and len(config.model['corrupt_type']) == 0:          # main.py:51-55 (pretraining configs only)
         config.model['corrupt_type'] = config.dataset['train']['others']['corrupt_type']
     assert config.total_bs % args.world_size == 0
     config.dataset.train.others.bs = config.total_bs // args.world_size
     set_random_seed(args.seed + args.local_rank, deterministic=args.deterministic)   # main.py:78-81
-    run_net(args, config)
+    if finetune:
+        runner_finetune.run_net(args, config)                              # main.py:96-103
+    else:
+        runner_pretrain.run_net(args, config)
 
 
 if __name__ == '__main__':

@@ -39,17 +39,27 @@ class FlatAdamW:
         for g in self.param_groups:
             g.setdefault('initial_lr', lr)
 
-    def step(self):
+    def step(self, grad_scale=None):
+        """grad_scale: an optional fp32 device scalar the gradients are multiplied by before the update (the
+        coefficient of finetune_ops.GradNormClip, i.e. clip_grad_norm_ then step) -- read on the device."""
         self.steps += 1
         m = self.model
+        if grad_scale is not None:
+            _lib.require(grad_scale, 'grad_scale')
+            if grad_scale.numel() != 1:
+                raise ValueError('FlatAdamW.step: grad_scale must be a one-element tensor')
         for g in self.param_groups:
             a, b = g['range']
             if b <= a:
                 continue
-            _lib.call('pdae_adamw_step', m.flat_param, b - a, m.flat_param[a:].data_ptr(),
-                      m.flat_grad[a:].data_ptr(), self.exp_avg[a:].data_ptr(), self.exp_avg_sq[a:].data_ptr(),
-                      float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']),
-                      float(g['weight_decay']), self.steps)
+            args = (m.flat_param, b - a, m.flat_param[a:].data_ptr(),
+                    m.flat_grad[a:].data_ptr(), self.exp_avg[a:].data_ptr(), self.exp_avg_sq[a:].data_ptr(),
+                    float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']),
+                    float(g['weight_decay']), self.steps)
+            if grad_scale is None:
+                _lib.call('pdae_adamw_step', *args)
+            else:
+                _lib.call('pdae_adamw_step_gscale', *args, grad_scale.data_ptr())
 
     def zero_grad(self, set_to_none=False):
         self.model.zero_grad()

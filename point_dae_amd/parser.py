@@ -1,5 +1,5 @@
 """Command line of main.py: the flags of the reference's utils/parser.py:7-104
-that matter on the pretraining path, same names and defaults."""
+that matter on the pretraining and fine-tuning paths, same names and defaults."""
 import argparse
 import os
 from pathlib import Path
@@ -22,6 +22,8 @@ def get_args(argv=None):
     p.add_argument('--val_freq', type=int, default=1, help='test freq')
     p.add_argument('--resume', action='store_true', default=False)
     p.add_argument('--total_bs', type=int, default=-1)
+    p.add_argument('--finetune_model', action='store_true', default=False, help='finetune modelnet with pretrained weight')
+    p.add_argument('--scratch_model', action='store_true', default=False, help='training modelnet from scratch')
     # synthetic-data controls (no dataset ships with this repo)
     p.add_argument('--max_epoch', type=int, default=-1, help='override config.max_epoch')
     p.add_argument('--steps_per_epoch', type=int, default=None,
@@ -31,6 +33,8 @@ def get_args(argv=None):
     args = p.parse_args(argv)
     if args.resume and args.start_ckpts is not None:
         raise ValueError('--resume and --start_ckpts cannot be both activate')
+    if args.finetune_model and args.scratch_model:
+        raise ValueError('--finetune_model and --scratch_model cannot be both activate')
     if 'LOCAL_RANK' not in os.environ:
         os.environ['LOCAL_RANK'] = str(args.local_rank)
     else:

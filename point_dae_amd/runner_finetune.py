@@ -1,0 +1,160 @@
+"""Classification fine-tuning loop (tools/runner_finetune.py:81-318 of the reference).
+
+Same control flow: FPS of every cloud to `point_all` points, a host np.random.choice of `npoints` of them, the gather;
+forward, cross-entropy, backward; the gradient-norm clip (clip_grad_norm_ with `grad_norm_clip`) then AdamW; the
+epoch-granular CosLR; validation on the test set with FPS to `npoints`, argmax accuracy, ckpt-best / ckpt-last.  The
+clip coefficient stays on the device (finetune_ops.GradNormClip -> FlatAdamW grad_scale), and loss / accuracy are
+accumulated on the device and read back once per log line, where the reference calls .item() twice per step.
+"""
+import time
+
+import numpy as np
+import torch
+
+from . import builder, dist_utils
+from . import datasets  # noqa: F401  (registers the synthetic ModelNet set)
+from .data_parallel import FlatDataParallel
+from .finetune_ops import GradNormClip
+from .misc import fps
+from .pointnet2_utils import furthest_point_sample, gather_operation
+from .registry import DATASETS
+from .svm_probe import Acc_Metric
+
+POINT_ALL = {1024: 1200, 2048: 2400, 4096: 4800, 8192: 8192}      # runner_finetune.py:160-171
+
+
+def subset_indices(npoints, point_all):
+    """The host draw of runner_finetune.py:174: npoints of the point_all FPS indices, without replacement."""
+    return np.random.choice(point_all, npoints, False)
+
+
+def resample(points, npoints, choice=None):
+    """FPS of each cloud to point_all points, then the columns `choice` (default: a fresh host draw) of the FPS
+    order, gathered -> (B, npoints, 3) (runner_finetune.py:158-176)."""
+    if npoints not in POINT_ALL:
+        raise NotImplementedError('npoints %d' % npoints)
+    point_all = min(POINT_ALL[npoints], points.shape[1])
+    xyz = points[:, :, :3].contiguous()
+    fps_idx = furthest_point_sample(xyz, point_all)
+    if choice is None:
+        choice = subset_indices(npoints, point_all)
+    choice = torch.as_tensor(choice, dtype=torch.int64).to(points.device, non_blocking=True)
+    idx = fps_idx.index_select(1, choice).contiguous()
+    return gather_operation(xyz.transpose(1, 2).contiguous(), idx).transpose(1, 2).contiguous()
+
+
+def train_step(model, optimizer, clip, points, labels):
+    """One optimisation step: forward, loss, backward, [gradient all-reduce], clip coefficient, AdamW.
+    -> (loss, acc) device scalars."""
+    base = model.module if isinstance(model, FlatDataParallel) else model
+    ret = model(points)
+    loss, acc = base.get_loss_acc(ret, labels)
+    loss.backward()
+    if isinstance(model, FlatDataParallel):
+        model.finish()                                  # the norm is taken after the all-reduce, as DDP + clip do
+    optimizer.step(grad_scale=clip() if clip is not None else None)
+    model.zero_grad()
+    return loss.detach(), acc.detach()
+
+
+@torch.no_grad()
+def validate(base_model, test_loader, epoch, config, args=None, log=print):
+    """runner_finetune.py:273-318: FPS to npoints, eval forward, argmax accuracy over the whole test set."""
+    base_model.eval()
+    preds, labels = [], []
+    for _, _, data in test_loader:
+        points, label = data[0].cuda(), data[1].cuda()
+        _, points = fps(points, config.npoints)
+        preds.append(base_model(points).argmax(-1).view(-1))
+        labels.append(label.view(-1))
+    pred, label = torch.cat(preds), torch.cat(labels)
+    if args is not None and getattr(args, 'distributed', False):
+        pred, label = dist_utils.gather_tensor(pred, args), dist_utils.gather_tensor(label, args)
+    acc = float((pred == label).sum().item()) / float(label.numel()) * 100.
+    log('[Validation] EPOCH: %d  acc = %.4f' % (epoch, acc))
+    return Acc_Metric(acc)
+
+
+def _loader(node, device, seed, rank, world, bs, steps_per_epoch=None):
+    c = dict(node._base_)
+    c.update(dict(node.others))
+    # ModelNetDataset yields N_POINTS points per cloud (the config's npoints is what the runner samples from them)
+    c['npoints'] = int(c.get('N_POINTS', c.get('npoints', 1024)))
+    c.update(device=device, seed=seed, rank=rank, world=world)
+    if steps_per_epoch is not None:
+        c.update(count=steps_per_epoch * bs)
+    c.setdefault('bs', bs)
+    return DATASETS.build(c)
+
+
+def run_net(args, config, log=print, log_every=20):
+    rank, world = dist_utils.get_dist_info()
+    device = torch.device('cuda', torch.cuda.current_device())
+    from .graph_step import use_created_stream
+    use_created_stream(device)
+    bs = config.total_bs // world
+    spe = getattr(args, 'steps_per_epoch', None)
+    train_loader = _loader(config.dataset.train, device, args.seed + rank, rank, world, bs, spe)
+    test_loader = _loader(config.dataset.test if config.dataset.get('test') is not None else config.dataset.val,
+                          device, args.seed, rank, world, bs)
+
+    base_model = builder.model_builder(config.model)
+    start_epoch, best_metric = 0, 0.
+    if args.resume:
+        start_epoch, best_metric = builder.resume_model(base_model, args)
+    elif args.ckpts is not None:
+        base_model.load_model_from_ckpt(args.ckpts, log=log)           # runner_finetune.py:100-101
+    else:
+        base_model.load_model_from_ckpt(None, log=log)
+    base_model = base_model.to(device)
+    model = FlatDataParallel(base_model)
+    optimizer, scheduler = builder.build_opti_sche(model, config)
+    from .optim import FlatAdamW
+    if not isinstance(optimizer, FlatAdamW):
+        raise NotImplementedError('runner_finetune: the fused AdamW (optimizer.part: all) is the only optimiser that '
+                                  'reads the device-side clip coefficient; part %r is not supported'
+                                  % config.optimizer.get('part', 'all'))
+    model.zero_grad()
+    clip = GradNormClip(model.flat_grad, config.grad_norm_clip) if config.get('grad_norm_clip') is not None else None
+    if int(config.get('step_per_update', 1)) != 1:
+        raise NotImplementedError('runner_finetune: step_per_update > 1 (gradient accumulation) is not supported')
+    best_metrics, metrics = Acc_Metric(best_metric), Acc_Metric(0.)
+    # the step is replayed as a hipGraph (graph_step.GraphedClassifierStep); a short last batch steps eagerly
+    from .graph_step import GraphedClassifierStep
+    graphed = GraphedClassifierStep(model, optimizer, clip, bs, config.npoints)
+    if rank == 0:
+        log('step: hipGraph replay (GraphedClassifierStep)')
+
+    for epoch in range(start_epoch, config.max_epoch + 1):
+        model.train()
+        if hasattr(train_loader, 'set_epoch'):
+            train_loader.set_epoch(epoch)
+        acc_sum = torch.zeros(2, device=device)
+        t0, n = time.time(), 0
+        for idx, (_, _, data) in enumerate(train_loader):
+            points = resample(data[0], config.npoints)
+            if points.shape[0] == bs:
+                loss, acc = graphed(points, data[1])
+            else:
+                loss, acc = train_step(model, optimizer, clip, points, data[1])
+            acc_sum += torch.stack([loss, acc])
+            n += 1
+            if (idx + 1) % log_every == 0 or idx + 1 == len(train_loader):
+                vals = acc_sum.clone()
+                if world > 1:
+                    vals = dist_utils.reduce_tensor(vals, args)
+                vals = (vals / n).tolist()                   # one host sync per log line
+                if rank == 0:
+                    log('[Epoch %d/%d][Batch %d/%d] %.1f clouds/s Loss = %.4f Acc = %.4f lr = %.6f' % (
+                        epoch, config.max_epoch, idx + 1, len(train_loader), n * bs * world / (time.time() - t0),
+                        vals[0], vals[1], optimizer.param_groups[0]['lr']))
+        for item in (scheduler if isinstance(scheduler, list) else [scheduler]):
+            if item is not None:
+                item.step(epoch)
+        if epoch % max(int(getattr(args, 'val_freq', 1)), 1) == 0:
+            metrics = validate(base_model, test_loader, epoch, config, args, log=log)
+            if metrics.better_than(best_metrics):
+                best_metrics = metrics
+                builder.save_checkpoint(model, optimizer, epoch, metrics, best_metrics, 'ckpt-best', args)
+        builder.save_checkpoint(model, optimizer, epoch, metrics, best_metrics, 'ckpt-last', args)
+    return model

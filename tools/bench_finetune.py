@@ -1,0 +1,101 @@
+"""Times the classification fine-tuning step (point_transformer.PointTransformer on the ModelNet40 fine-tuning config,
+B=32, N=1024, G=64) and prints ONE JSON line:
+
+  graphed / eager   ms per optimisation step (forward, cross-entropy, backward, clip coefficient, AdamW) and clouds/s,
+                    HIP events around `--steps` steps after `--warmup` untimed ones; the input batch is resampled in front
+                    of the timed region (the loader's work is not part of the step)
+  grad_norm_clip_us / adamw_step_gscale_us   one launch pair of each over the flat gradient / parameter buffers, HIP
+                    events around `--reps` back-to-back calls
+  kernels_per_step  device kernels of one eager step (torch.profiler), null where the profiler records none
+
+    timeout -k 10 300 python tools/bench_finetune.py [--steps 30 --warmup 10 --reps 50]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _events_ms(fn, n):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument('--steps', type=int, default=30)
+    p.add_argument('--warmup', type=int, default=10)
+    p.add_argument('--reps', type=int, default=50)
+    p.add_argument('--batch', type=int, default=32)
+    a = p.parse_args(argv)
+    import torch
+    from point_dae_amd import builder
+    from point_dae_amd.config import cfg_from_yaml_file
+    from point_dae_amd.data_parallel import FlatDataParallel
+    from point_dae_amd.finetune_ops import GradNormClip
+    from point_dae_amd.graph_step import GraphedClassifierStep, use_created_stream
+    from point_dae_amd.runner_finetune import resample, train_step
+    from point_dae_amd.synthetic import labelled_clouds
+
+    config = cfg_from_yaml_file(os.path.join(ROOT, 'cfgs', 'finetune_modelnet_transferring_features.yaml'))
+    B, N = a.batch, config.npoints
+    dev = torch.device('cuda', 0)
+    torch.cuda.set_device(dev)
+    use_created_stream(dev)
+    x, y = labelled_clouds(B, 2048, seed=0, classes=3)
+    pts = resample(torch.from_numpy(x).to(dev), N)
+    labels = torch.from_numpy(y).to(dev)
+    out = dict(workload='finetune_modelnet', batch=B, npoints=N, num_group=config.model.num_group,
+               tokens=config.model.num_group + 1, depth=config.model.depth, steps=a.steps, warmup=a.warmup)
+
+    def setup():
+        torch.manual_seed(0)
+        net = builder.model_builder(config.model).to(dev).train()
+        model = FlatDataParallel(net)
+        opt, _ = builder.build_opti_sche(model, config)
+        model.zero_grad()
+        return model, opt, GradNormClip(model.flat_grad, config.grad_norm_clip)
+
+    model, opt, clip = setup()
+    for _ in range(a.warmup):
+        train_step(model, opt, clip, pts, labels)
+    ms = _events_ms(lambda: train_step(model, opt, clip, pts, labels), a.steps)
+    out['eager'] = dict(ms_per_step=round(ms, 4), clouds_per_s=round(B / ms * 1e3, 1))
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            train_step(model, opt, clip, pts, labels)
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if e.device_type.name == 'CUDA')
+        out['kernels_per_step'] = n or None
+    except Exception as e:                           # a profiler without a device tracer
+        out['kernels_per_step'] = None
+        out['kernels_per_step_error'] = type(e).__name__
+
+    model, opt, clip = setup()
+    step = GraphedClassifierStep(model, opt, clip, B, N)
+    for _ in range(a.warmup):
+        step(pts, labels)
+    ms = _events_ms(lambda: step(pts, labels), a.steps)
+    out['graphed'] = dict(ms_per_step=round(ms, 4), clouds_per_s=round(B / ms * 1e3, 1))
+
+    coef = clip()
+    out['flat_params'] = model.flat_grad.numel()
+    out['grad_norm_clip_us'] = round(_events_ms(clip, a.reps) * 1e3, 2)
+    out['grad_norm_clip_GBps'] = round(4.0 * model.flat_grad.numel() / (out['grad_norm_clip_us'] * 1e-6) / 1e9, 1)
+    out['adamw_step_gscale_us'] = round(_events_ms(lambda: opt.step(grad_scale=coef), a.reps) * 1e3, 2)
+    out['device'] = torch.cuda.get_device_name(dev)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
