@@ -12,37 +12,13 @@
 // the ReLU mask); one pass over it produces dp[b,c] = sum_g dpre and per-block partials of
 // dgd[g] = sum_{b,c} dpre (added in block order by the caller: no atomics); da[b] = sum_c dp[b,c]
 // is a reduction of the small dp.
-#include <cstdlib>
-
 #include "common.h"
 
 namespace pdae {
 
-// one float4 of the output per thread; consecutive threads walk a row
-__global__ __launch_bounds__(256) void fold_input_kernel(long long n4, int coarse, int cells, int C4,
-                                                         const float4* __restrict__ a,
-                                                         const float4* __restrict__ p,
-                                                         const float4* __restrict__ gd,
-                                                         float4* __restrict__ h) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const long long row = i / C4;
-  const int q = (int)(i - row * C4);
-  const long long bc = row / cells;
-  const int g = (int)(row - bc * cells);
-  const long long b = bc / coarse;
-  const float4 va = a[b * C4 + q], vp = p[bc * C4 + q], vg = gd[(long long)g * C4 + q];
-  float4 o;
-  o.x = (va.x + vp.x) + vg.x, o.y = (va.y + vp.y) + vg.y;
-  o.z = (va.z + vp.z) + vg.z, o.w = (va.w + vp.w) + vg.w;
-  o.x = o.x > 0.f ? o.x : 0.f, o.y = o.y > 0.f ? o.y : 0.f;
-  o.z = o.z > 0.f ? o.z : 0.f, o.w = o.w > 0.f ? o.w : 0.f;
-  h[i] = o;
-}
-
-// The same pass with the per-pair work hoisted (round 6): a thread owns one channel quad of one (cloud, coarse point) pair,
+// The pass with the per-pair work hoisted (round 6): a thread owns one channel quad of one (cloud, coarse point) pair,
 // adds a[b] + p[b,c] ONCE and walks the pair's cells -- 1 + 1/cells loads per store instead of 3, `cells` stores in flight
-// per thread; the one-float4-per-thread form above ran the 4.3 GB write at 3.4 TB/s (a million 256-thread blocks).
+// per thread; a one-float4-per-thread form ran the 4.3 GB write at 3.4 TB/s (a million 256-thread blocks).
 __global__ __launch_bounds__(256) void fold_input_pairs_kernel(long long pairs4, int coarse, int cells, int C4,
                                                                const float4* __restrict__ a, const float4* __restrict__ p,
                                                                const float4* __restrict__ gd, float4* __restrict__ h) {
@@ -138,17 +114,10 @@ extern "C" int pdae_fold_input(int clouds, int coarse, int cells, int C, const f
   if (!a || !p || !gd || !h) return bad_arg("fold_input: null pointer");
   const long long n4 = (long long)clouds * coarse * cells * (C / 4);
   if ((n4 + 255) / 256 > 0x7fffffffLL) return unsupported("fold_input: too many elements");
-  static const bool per_element = [] { const char* e = getenv("PDAE_FOLD_INPUT"); return e && e[0] == 'e'; }();   // (A/B)
-  if (per_element) {
-    hipLaunchKernelGGL(fold_input_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, as_stream(stream), n4,
-                       coarse, cells, C / 4, reinterpret_cast<const float4*>(a), reinterpret_cast<const float4*>(p),
-                       reinterpret_cast<const float4*>(gd), reinterpret_cast<float4*>(h));
-  } else {
-    const long long pairs4 = (long long)clouds * coarse * (C / 4);
-    hipLaunchKernelGGL(fold_input_pairs_kernel, dim3((unsigned)((pairs4 + 255) / 256)), dim3(256), 0, as_stream(stream),
-                       pairs4, coarse, cells, C / 4, reinterpret_cast<const float4*>(a), reinterpret_cast<const float4*>(p),
-                       reinterpret_cast<const float4*>(gd), reinterpret_cast<float4*>(h));
-  }
+  const long long pairs4 = (long long)clouds * coarse * (C / 4);
+  hipLaunchKernelGGL(fold_input_pairs_kernel, dim3((unsigned)((pairs4 + 255) / 256)), dim3(256), 0, as_stream(stream),
+                     pairs4, coarse, cells, C / 4, reinterpret_cast<const float4*>(a), reinterpret_cast<const float4*>(p),
+                     reinterpret_cast<const float4*>(gd), reinterpret_cast<float4*>(h));
   return check_launch("fold_input");
 }
 

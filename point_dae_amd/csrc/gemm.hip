@@ -795,8 +795,7 @@ extern "C" int pdae_conv_stats(int M, int N, int K, const float* X, const float*
   (void)hipMemsetAsync(stats, 0, sizeof(float) * 16 * (size_t)N, s);
   if (M == 0) return check_launch("conv_stats");
   if (!X || !W || !Y) return bad_arg("conv_stats: null pointer");
-  static const bool k4_off = [] { const char* e = getenv("PDAE_CONV_K4"); return e && e[0] == '0'; }();     // (A/B)
-  if (K == 4 && !scale && !k4_off && N % 4 == 0 && N <= 1024 && 256 % (N / 4) == 0 && !(((uintptr_t)X | (uintptr_t)W | (uintptr_t)Y) & 15)) {
+  if (K == 4 && !scale && N % 4 == 0 && N <= 1024 && 256 % (N / 4) == 0 && !(((uintptr_t)X | (uintptr_t)W | (uintptr_t)Y) & 15)) {
     const int blocks = (M + K4_ROWS - 1) / K4_ROWS, phases = 256 / (N / 4);
     float* det = static_cast<float*>(det_workspace(sizeof(float) * (size_t)blocks * 2 * N, &rc));
     if (rc) return rc;

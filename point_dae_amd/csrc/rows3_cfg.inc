@@ -6,8 +6,9 @@
 namespace pdae {
 namespace rows3 {
 
+// -> gridDim.x of the launch
 template <int TI, int TJ, int WM, int WN, int KS, bool BKN, int EPI, bool PERS>
-static void launch_cfg3_k(Args& a, int nslots, int splits, size_t lds, hipStream_t s) {
+static int launch_cfg3_k(Args& a, int nslots, int splits, size_t lds, hipStream_t s) {
   auto k = gemm3_kernel<TI, TJ, WM, WN, KS, BKN, EPI, true, 0, PERS>;
   static size_t set_to = 0;                            // (EPI_BNRELU_STATS: the size depends on N)
   if (lds > set_to) {
@@ -15,10 +16,12 @@ static void launch_cfg3_k(Args& a, int nslots, int splits, size_t lds, hipStream
     set_to = lds;
   }
   hipLaunchKernelGGL(k, dim3(8 * nslots, splits, 1), dim3(WM * WN * 64), lds, s, a);
+  return 8 * nslots;
 }
 
+// -> gridDim.x of the launch; a.tiles holds its tile count
 template <int TI, int TJ, int WM, int WN, int KS, bool BKN, int EPI>
-static void launch_cfg3(Args& a, int splits, int stream_blocks, hipStream_t s) {
+static int launch_cfg3(Args& a, int splits, int stream_blocks, hipStream_t s) {
   constexpr int BM = 32 * TI * WM, BN = 32 * TJ * WN;
   a.tiles_n = (a.N + BN - 1) / BN;
   a.tiles = ((a.M + BM - 1) / BM) * a.tiles_n;
@@ -34,25 +37,26 @@ static void launch_cfg3(Args& a, int splits, int stream_blocks, hipStream_t s) {
   // nothing of the tile loop in the k-loop)
   const int kt = a.kchunk / (16 * KS), per_xcd = 32 / splits > 0 ? 32 / splits : 1;
   if (kt % 2 == 0 && kt >= 4 && a.K % a.kchunk == 0 && chunk > per_xcd)
-    launch_cfg3_k<TI, TJ, WM, WN, KS, BKN, EPI, true>(a, per_xcd, splits, lds, s);
-  else launch_cfg3_k<TI, TJ, WM, WN, KS, BKN, EPI, false>(a, chunk, splits, lds, s);
+    return launch_cfg3_k<TI, TJ, WM, WN, KS, BKN, EPI, true>(a, per_xcd, splits, lds, s);
+  return launch_cfg3_k<TI, TJ, WM, WN, KS, BKN, EPI, false>(a, chunk, splits, lds, s);
 }
 
-void R3_NAME(Args& a, bool w_kn, int epi, int splits, hipStream_t s) {
+// -> gridDim.x of the launch, 0 when this tile shape does not carry the epilogue (nothing launched)
+int R3_NAME(Args& a, bool w_kn, int epi, int splits, hipStream_t s) {
   constexpr int TI = R3_TI, TJ = R3_TJ, WM = R3_WM, WN = R3_WN, KS = R3_KS;
   if (!w_kn) {
-    if (epi == rows::EPI_STORE) launch_cfg3<TI, TJ, WM, WN, KS, false, rows::EPI_STORE>(a, splits, 0, s);
-    else if (epi == rows::EPI_BIAS_RELU) launch_cfg3<TI, TJ, WM, WN, KS, false, rows::EPI_BIAS_RELU>(a, splits, 0, s);
-    else if (epi == rows::EPI_MUL_POS) launch_cfg3<TI, TJ, WM, WN, KS, false, rows::EPI_MUL_POS>(a, splits, 0, s);
-    else launch_cfg3<TI, TJ, WM, WN, KS, false, rows::EPI_BIAS_GELU2>(a, splits, 0, s);
-  } else {
-    if (epi == rows::EPI_STORE) launch_cfg3<TI, TJ, WM, WN, KS, true, rows::EPI_STORE>(a, splits, 0, s);
-    else if (epi == rows::EPI_BNRELU_STATS) {
-      if constexpr (TJ <= 2 && WM == 4 && WN == 2) launch_cfg3<TI, TJ, WM, WN, KS, true, rows::EPI_BNRELU_STATS>(a, splits, 0, s);
-    }
-    else if (epi == rows::EPI_MUL_POS) launch_cfg3<TI, TJ, WM, WN, KS, true, rows::EPI_MUL_POS>(a, splits, 0, s);
-    else launch_cfg3<TI, TJ, WM, WN, KS, true, rows::EPI_MUL_GELUGRAD>(a, splits, 0, s);
+    if (epi == rows::EPI_STORE) return launch_cfg3<TI, TJ, WM, WN, KS, false, rows::EPI_STORE>(a, splits, 0, s);
+    if (epi == rows::EPI_BIAS_RELU) return launch_cfg3<TI, TJ, WM, WN, KS, false, rows::EPI_BIAS_RELU>(a, splits, 0, s);
+    if (epi == rows::EPI_MUL_POS) return launch_cfg3<TI, TJ, WM, WN, KS, false, rows::EPI_MUL_POS>(a, splits, 0, s);
+    return launch_cfg3<TI, TJ, WM, WN, KS, false, rows::EPI_BIAS_GELU2>(a, splits, 0, s);
   }
+  if (epi == rows::EPI_STORE) return launch_cfg3<TI, TJ, WM, WN, KS, true, rows::EPI_STORE>(a, splits, 0, s);
+  if (epi == rows::EPI_BNRELU_STATS) {
+    if constexpr (TJ <= 2 && WM == 4 && WN == 2) return launch_cfg3<TI, TJ, WM, WN, KS, true, rows::EPI_BNRELU_STATS>(a, splits, 0, s);
+    else return 0;
+  }
+  if (epi == rows::EPI_MUL_POS) return launch_cfg3<TI, TJ, WM, WN, KS, true, rows::EPI_MUL_POS>(a, splits, 0, s);
+  return launch_cfg3<TI, TJ, WM, WN, KS, true, rows::EPI_MUL_GELUGRAD>(a, splits, 0, s);
 }
 
 }  // namespace rows3

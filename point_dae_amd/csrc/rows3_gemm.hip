@@ -20,18 +20,18 @@ size_t lds_bytes3(const Cfg3& c) {
   return (size_t)2 * 3 * (bm + bn) * (c.ks == 2 ? 80 : 48);
 }
 
-void launch_rows3_cfg0(Args& a, bool w_kn, int epi, int splits, hipStream_t s);
-void launch_rows3_cfg1(Args& a, bool w_kn, int epi, int splits, hipStream_t s);
-void launch_rows3_cfg2(Args& a, bool w_kn, int epi, int splits, hipStream_t s);
-void launch_rows3_cfg3(Args& a, bool w_kn, int epi, int splits, hipStream_t s);
+int launch_rows3_cfg0(Args& a, bool w_kn, int epi, int splits, hipStream_t s);
+int launch_rows3_cfg1(Args& a, bool w_kn, int epi, int splits, hipStream_t s);
+int launch_rows3_cfg2(Args& a, bool w_kn, int epi, int splits, hipStream_t s);
+int launch_rows3_cfg3(Args& a, bool w_kn, int epi, int splits, hipStream_t s);
 
-void launch_gemm3(Args& a, int cfg, bool w_kn, int epi, int splits, int stream_blocks, hipStream_t s) {
+int launch_gemm3(Args& a, int cfg, bool w_kn, int epi, int splits, int stream_blocks, hipStream_t s) {
   (void)stream_blocks;
   switch (cfg) {
-    case 0: launch_rows3_cfg0(a, w_kn, epi, splits, s); break;
-    case 1: launch_rows3_cfg1(a, w_kn, epi, splits, s); break;
-    case 2: launch_rows3_cfg2(a, w_kn, epi, splits, s); break;
-    default: launch_rows3_cfg3(a, w_kn, epi, splits, s); break;
+    case 0: return launch_rows3_cfg0(a, w_kn, epi, splits, s);
+    case 1: return launch_rows3_cfg1(a, w_kn, epi, splits, s);
+    case 2: return launch_rows3_cfg2(a, w_kn, epi, splits, s);
+    default: return launch_rows3_cfg3(a, w_kn, epi, splits, s);
   }
 }
 

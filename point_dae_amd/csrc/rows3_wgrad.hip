@@ -1,17 +1,13 @@
 // rows3_wgrad.hip -- the grouped weight gradients on exact-split bf16 (rows3_kernel.h wgrad3b_kernel)
-#include <cstdlib>
-
 #include "rows3_kernel.h"
 
 namespace pdae {
 namespace rows3 {
 
 // The row-staged kernel (wgrad3t_kernel: 16-byte row loads, transposed fragment reads) takes every group whose widths are
-// multiples of 8 and whose operands are 16-byte aligned -- every weight gradient of the shipped models; PDAE_WGRAD3=b
-// keeps the column-patch kernel (A/B runs).
+// multiples of 8 and whose operands are 16-byte aligned -- every weight gradient of the shipped models; the others take
+// the column-patch kernel (wgrad3b_kernel).
 static bool row_staged_ok(const rows::WgradArgs& g) {
-  static const bool forced_b = [] { const char* e = getenv("PDAE_WGRAD3"); return e && e[0] == 'b'; }();
-  if (forced_b) return false;
   for (int i = 0; i < g.nprob; ++i) {
     const rows::WgradProb& p = g.p[i];
     if (p.N % 8 || p.K % 8 || ((uintptr_t)p.dY & 15) || ((uintptr_t)p.X & 15)) return false;

@@ -204,7 +204,8 @@ constexpr int NCFG3 = 4;
 constexpr int CFG3_BASE = 16;            // plan / pdae_rows_gemm `cfg` values CFG3_BASE + i select tile shape i of this family
 extern const Cfg3 kCfg3[NCFG3];
 size_t lds_bytes3(const Cfg3& c);
-void launch_gemm3(rows::Args& a, int cfg, bool w_kn, int epi, int splits, int stream_blocks, hipStream_t s);
+// -> gridDim.x of the launch (0: the tile shape does not carry that epilogue, nothing launched); a.tiles = its tile count
+int launch_gemm3(rows::Args& a, int cfg, bool w_kn, int epi, int splits, int stream_blocks, hipStream_t s);
 void launch_wgrad3(const rows::WgradArgs& g, int tn, int pl, hipStream_t s);
 }  // namespace rows3
 // the arithmetic in force for the forward / data-gradient half of the family (rows_gemm.hip)

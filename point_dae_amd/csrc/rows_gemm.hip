@@ -776,15 +776,9 @@ extern "C" int pdae_set_gemm_arith(int arith) {
   return PDAE_OK;
 }
 extern "C" int pdae_gemm_arith(void) { return gemm_arith(); }
-// (lab) PDAE_GEMM_ONLY=rows | wgrad: the exact-split arithmetic for that half of the family only
-static int arith_of(bool wgrad) {
-  static const char* only = getenv("PDAE_GEMM_ONLY");
-  if (only && gemm_arith() == PDAE_GEMM_BF16X3 && (wgrad ? strcmp(only, "wgrad") : strcmp(only, "rows")) != 0) return PDAE_GEMM_F32MFMA;
-  return gemm_arith();
-}
 
 namespace pdae {
-int gemm_arith_rows() { return arith_of(false); }
+int gemm_arith_rows() { return gemm_arith(); }
 }  // namespace pdae
 
 // shapes the exact-split kernels take: the reduction in whole 32-deep tiles (every layer of the models but the K = 3
@@ -814,9 +808,6 @@ static double plan3_cost(int M, int N, int K, int c3, int splits) {
 static void plan_rows3(int M, int N, int K, int may_split, int* cfg, int* splits, int* stream_blocks) {
   double best = 1e300;
   *cfg = rows3::CFG3_BASE, *splits = 1, *stream_blocks = 0;
-  static const char* force = getenv("PDAE_ROWS3_FORCE");       // lab: "cfg,splits" overrides every plan
-  int fc = -1, fs = -1;
-  if (force) sscanf(force, "%d,%d", &fc, &fs);
   const int smax = may_split <= 0 ? 1 : (may_split == 1 ? 4 : (may_split > 8 ? 8 : may_split));
   for (int c = 0; c < rows3::NCFG3; ++c)
     for (int s = 1; s <= smax; ++s) {
@@ -824,17 +815,12 @@ static void plan_rows3(int M, int N, int K, int may_split, int* cfg, int* splits
       const double t = plan3_cost(M, N, K, c, s);
       if (t < best * 0.995) best = t, *cfg = rows3::CFG3_BASE + c, *splits = s;
     }
-  if (fc >= 0) *cfg = rows3::CFG3_BASE + fc;
-  if (fs >= 1 && may_split) {                                  // (a forced split count still leaves every slab a tile)
-    while (fs > 1 && (long long)(fs - 1) * (((K + fs - 1) / fs + 31) / 32 * 32) >= K) --fs;
-    *splits = fs;
-  }
 }
 
 extern "C" int pdae_rows_gemm_plan(int M, int N, int K, int w_kn, int may_split, int* cfg, int* splits,
                                    int* stream_blocks) {
   if (M < 0 || N <= 0 || K <= 0 || !cfg || !splits || !stream_blocks) return bad_arg("rows_gemm_plan: bad argument");
-  if (arith_of(false) == PDAE_GEMM_BF16X3 && gemm3_takes(N, K, w_kn != 0))
+  if (gemm_arith() == PDAE_GEMM_BF16X3 && gemm3_takes(N, K, w_kn != 0))
     plan_rows3(M > 0 ? M : 1, N, K, may_split, cfg, splits, stream_blocks);
   else plan_rows(M > 0 ? M : 1, N, K, w_kn != 0, may_split != 0, cfg, splits, stream_blocks);
   return PDAE_OK;
@@ -859,7 +845,7 @@ extern "C" int pdae_rows_gemm(int M, int N, int K, const float* X, const float* 
   }
   if (cfg < 0 || splits < 0) {
     int c, s, b;
-    if (arith_of(false) == PDAE_GEMM_BF16X3 && gemm3_takes(N, K, w_kn != 0)) plan_rows3(M > 0 ? M : 1, N, K, 0, &c, &s, &b);
+    if (gemm_arith() == PDAE_GEMM_BF16X3 && gemm3_takes(N, K, w_kn != 0)) plan_rows3(M > 0 ? M : 1, N, K, 0, &c, &s, &b);
     else plan_rows(M > 0 ? M : 1, N, K, w_kn != 0, false, &c, &s, &b);
     if (cfg < 0) cfg = c;
     if (splits < 0) splits = 1, stream_blocks = 0;
@@ -978,20 +964,17 @@ extern "C" int pdae_rows_gemm_bnrelu_stats(int M, int N, int K, const float* dY,
   if (groups && M % 32 != 0) return bad_arg("rows_gemm_bnrelu_stats: a group list needs M % 32 == 0");
   if ((long long)M * (K > N ? K : N) >= (1LL << 30) || (long long)N * K >= (1LL << 30))
     return unsupported("rows_gemm_bnrelu_stats: 32-bit byte offsets");
-  // the grid launch_cfg3 will choose: persistent (8 x 32 blocks) when the stream of LDS tiles keeps its parity, else one
-  // block per tile; 128 x 64 tiles for the narrow layers, 128 x 128 else (the two shapes that carry this epilogue)
-  const int c3 = N <= 64 ? 3 : 0, bn = N <= 64 ? 64 : 128;
-  const int tiles = ((M + 127) / 128) * ((N + bn - 1) / bn), chunk = (tiles + 7) / 8, kt = K / 32;
-  const bool pers = kt % 2 == 0 && kt >= 4 && chunk > 32;
-  // (one partial row per BLOCK; a one-tile-per-block launch of thousands of tiles -- a reduction too short for the
-  // persistent form -- hands the finishing pass as many rows: it then runs in two levels)
-  if (arith_of(false) == PDAE_GEMM_BF16X3 && gemm3_takes(N, K, true) && workspace && N <= 2048) {
+  // 128 x 64 tiles for the narrow layers, 128 x 128 else (the two shapes that carry this epilogue).  One partial row per
+  // BLOCK of the launch: a one-tile-per-block launch of thousands of tiles -- a reduction too short for the persistent
+  // form -- hands the finishing pass as many rows, and it then runs in two levels
+  if (gemm_arith() == PDAE_GEMM_BF16X3 && gemm3_takes(N, K, true) && workspace && N <= 2048) {
     Args a = {};
     a.M = M, a.N = N, a.K = K, a.A = dY, a.lda = K, a.B = W, a.ldb = N, a.C = T, a.ldc = N;
     a.Z = const_cast<float*>(X), a.slab = (long long)M * N;
     a.bn_scale = scale, a.bn_shift = shift, a.bn_mean = mean, a.bn_invstd = invstd, a.z_groups = groups, a.stats_part = workspace;
-    rows3::launch_gemm3(a, c3, true, EPI_BNRELU_STATS, 1, 0, s);
-    const int gx = 8 * (pers ? 32 : chunk), W2 = 2 * N;
+    const int gx = rows3::launch_gemm3(a, N <= 64 ? 3 : 0, true, EPI_BNRELU_STATS, 1, 0, s);
+    if (gx == 0) return unsupported("rows_gemm_bnrelu_stats: the tile shape does not carry the statistics epilogue");
+    const int tiles = a.tiles, W2 = 2 * N;
     if (gx > 1024) {
       const int P = (gx + 255) / 256;
       float* mid = workspace + (size_t)gx * W2;
@@ -1012,10 +995,8 @@ extern "C" int pdae_rows_gemm_bnrelu_stats(int M, int N, int K, const float* dY,
 // the widest tile every layer's K is a multiple of: 384 (the Transformer blocks: 384, 1536), 256 (FoldingNet, the
 // PointNet++ levels: 256, 512, 1024), else 128
 static int wgrad_tile_width(int nprob, const int* Ks) {
-  if (arith_of(true) == PDAE_GEMM_BF16X3) return 128;         // exact-split kernel: 128 x 128 tiles (two accumulator sets)
-  static const char* force = getenv("PDAE_WGRAD_TN");       // A/B switch (tools/lab/ab.sh): caps the tile width
-  const int cap = force ? atoi(force) : 384;
-  bool w384 = cap >= 384, w256 = cap >= 256;
+  if (gemm_arith() == PDAE_GEMM_BF16X3) return 128;         // exact-split kernel: 128 x 128 tiles (two accumulator sets)
+  bool w384 = true, w256 = true;
   for (int q = 0; q < nprob; ++q) {
     if (Ks[q] % 384 != 0) w384 = false;
     if (Ks[q] % 256 != 0) w256 = false;
@@ -1055,10 +1036,7 @@ static int wgrad_layout(int nprob, const int* Ms, const int* Ns, const int* Ks, 
     return PDAE_OK;
   }
   // one residency of the chip: 256 CUs x 2 blocks of 4 waves (128-wide tiles), x 1 block of 8 waves (384-wide)
-  int wg_blocks = (WTN >= 256 || arith_of(true) == PDAE_GEMM_BF16X3) ? 256 : 512;   // (the exact-split kernel: 8 waves, 122 KB of LDS)
-  // (lab) PDAE_WGRAD_BPT=k: k blocks per output tile instead of one residency of the chip
-  static const int bpt = getenv("PDAE_WGRAD_BPT") ? atoi(getenv("PDAE_WGRAD_BPT")) : 0;
-  if (bpt > 0) wg_blocks = (bpt * tiles + 7) / 8 * 8;
+  const int wg_blocks = (WTN >= 256 || gemm_arith() == PDAE_GEMM_BF16X3) ? 256 : 512;   // (the exact-split kernel: 8 waves, 122 KB of LDS)
   g->blocks = (int)(units < wg_blocks ? units : wg_blocks);
   if (g->blocks == 0) {
     g->slots = 1;
@@ -1107,8 +1085,7 @@ static void wgrad_order(int nprob, const int* Ms, int* perm) {
 }
 
 static int wgrad_head_tiles(int nprob, const int* Ms, const int* Ns, const int* Ks, int WTN) {
-  static const char* off = getenv("PDAE_WGRAD_SPLIT");        // lab: 0 switches the two-launch schedule off
-  if ((off && atoi(off) == 0) || arith_of(true) != PDAE_GEMM_BF16X3) return 0;
+  if (gemm_arith() != PDAE_GEMM_BF16X3) return 0;
   long long lead = 0, tiles = 0;
   bool run = true;
   for (int q = 0; q < nprob; ++q) {
@@ -1179,7 +1156,7 @@ extern "C" int pdae_rows_wgrad_multi(int nprob, const int* Ms, const float* cons
     for (int q = 0; q < nprob; ++q)
       a.p[q].dY = dY[perm[q]], a.p[q].X = X[perm[q]], a.p[q].dW = dW[perm[q]], a.p[q].db = db ? db[perm[q]] : nullptr;
   };
-  bool one_chunk = arith_of(true) == PDAE_GEMM_BF16X3 && head == 0;
+  bool one_chunk = gemm_arith() == PDAE_GEMM_BF16X3 && head == 0;
   for (int q = 0; q < nprob; ++q) one_chunk = one_chunk && Ms[q] <= WCH;
   if (one_chunk) {
     // every layer on at most 32 rows (the coarse heads' Linear layers on a batch of 32 clouds): a tile IS one unit, so a
@@ -1212,7 +1189,7 @@ extern "C" int pdae_rows_wgrad_multi(int nprob, const int* Ms, const float* cons
   for (int q = 1; q < nprob; ++q) max_chunks = g.p[q].chunks > max_chunks ? g.p[q].chunks : max_chunks;
   const long long most = (max_chunks * (long long)g.blocks + g.units - 1) / g.units + 1;
   const int pl = most <= 16 ? 1 : (most <= 64 ? 4 : 8);
-  if (arith_of(true) == PDAE_GEMM_BF16X3) rows3::launch_wgrad3(g, tn, pl, s);
+  if (gemm_arith() == PDAE_GEMM_BF16X3) rows3::launch_wgrad3(g, tn, pl, s);
   else if (tn == 384) wgrad_launch<384>(g, pl, s);
   else if (tn == 256) wgrad_launch<256>(g, pl, s);
   else wgrad_launch<128>(g, pl, s);
@@ -1238,7 +1215,7 @@ extern "C" int pdae_rows_wgrad_listed(int M, int N, int K, const float* dY, cons
   const long long most = (g.p[0].chunks * (long long)g.blocks + g.units - 1) / g.units + 1;
   const int pl = most <= 16 ? 1 : (most <= 64 ? 4 : 8);
   hipStream_t s = as_stream(stream);
-  if (arith_of(true) == PDAE_GEMM_BF16X3) rows3::launch_wgrad3(g, tn, pl, s);
+  if (gemm_arith() == PDAE_GEMM_BF16X3) rows3::launch_wgrad3(g, tn, pl, s);
   else if (tn == 384) wgrad_launch<384>(g, pl, s);
   else if (tn == 256) wgrad_launch<256>(g, pl, s);
   else wgrad_launch<128>(g, pl, s);
@@ -1290,8 +1267,7 @@ extern "C" int pdae_rows_gemm_batched(int batch, int M, int N, int K, const floa
   a.M = M, a.N = N, a.K = K, a.A = X, a.lda = K, a.B = W, a.ldb = K, a.C = Y, a.ldc = N;
   a.slab = (long long)M * N, a.strideA = strideX, a.strideB = strideW, a.strideC = strideY;
   hipStream_t s = as_stream(stream);
-  static const bool sym_off = getenv("PDAE_GRAM_SYMMETRIC") && atoi(getenv("PDAE_GRAM_SYMMETRIC")) == 0;   // lab: A/B switch
-  if (X == W && strideX == strideW && M == N && N % 4 == 0 && strideY % 4 == 0 && !sym_off &&
+  if (X == W && strideX == strideW && M == N && N % 4 == 0 && strideY % 4 == 0 &&
       (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
     // a Gram matrix X X^T: the 64 x 64 tiles on and above the diagonal, each stored a second time transposed (half the
     // products; G[j][i] is bit for bit the G[i][j] a tile of its own would compute)

@@ -84,7 +84,6 @@ class FlatDataParallel(nn.Module):
         self.sink_armed, self.sink_written = False, set()
         self.sink_strided = []          # (flat view, 2-D tile, cols): gradients the gather copies out of a wider tile
         self.wgrad_queue = []           # the armed step's queued weight gradients (nn_ops.flush_wgrad_queue)
-        self.wgrad_stream, self.wgrad_inflight = None, []     # optional side stream for them (graph_step)
         me = weakref.ref(self)
         for i, p in enumerate(params):
             p._pdae_flat = (me, i)

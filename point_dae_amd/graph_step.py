@@ -72,8 +72,6 @@ class _KeepBNState:
         return False
 
 
-SINK = os.environ.get('PDAE_GRAD_SINK', '1') != '0'
-WGRAD_SIDE = os.environ.get('PDAE_WGRAD_SIDE', '0') != '0'     # the stacks' weight gradients on a side stream (lab)
 _AVG_OK = {}
 
 
@@ -299,9 +297,7 @@ class GraphedTrainStep:
         # the blocks' weight gradients go straight into THIS model's flat buffer (nn_ops._sink_views): every .grad
         # is None here and nothing else touches the flat gradient views until the gather below
         from . import nn_ops
-        m.sink_armed, m.sink_written, m.sink_strided = SINK, set(), []
-        if WGRAD_SIDE and m.wgrad_stream is None:
-            m.wgrad_stream = torch.cuda.Stream()
+        m.sink_armed, m.sink_written, m.sink_strided = True, set(), []
         try:
             lx, ln = m(self.pts, self.pts, steps=self.steps,
                        rows=(self.vis[:nv], self.msk[:nm], self.vis32[:nv], self.msk32[:nm], self.order))
@@ -309,17 +305,14 @@ class GraphedTrainStep:
             # the 34 LayerNorm backward launches park their parameter-gradient partials; ONE launch adds them
             # all after the backward (include/pdae.h: deferred reductions) -- nothing reads those gradients
             # before the gather below
-            if SINK:
-                _lib.deferred_begin()
+            _lib.deferred_begin()
             try:
                 # (the seed of the backward pass is a constant: autograd's own ones_like is a fill launch per step)
                 loss.backward(self.seed if self.seed.shape == loss.shape and self.seed.dtype == loss.dtype else None)
                 nn_ops.flush_wgrad_queue(m)        # (stacks flush themselves; this catches a queue left by a cut)
-                nn_ops.join_wgrad_stream(m)
             finally:
                 m.wgrad_queue = []
-                if SINK:
-                    _lib.deferred_flush(lx)
+                _lib.deferred_flush(lx)
         finally:
             enc.grad_cut = None
             m.sink_armed = False
@@ -328,13 +321,11 @@ class GraphedTrainStep:
 
     def _phase2(self, cut):
         """the patch embedder's backward from the token gradient phase 1 left in cut['leaf'].grad"""
-        if SINK:
-            _lib.deferred_begin()
+        _lib.deferred_begin()
         try:
             cut['tokens'].backward(cut['leaf'].grad)
         finally:
-            if SINK:
-                _lib.deferred_flush(self.pts)
+            _lib.deferred_flush(self.pts)
         self._gather(self.late_idx)
         cut.clear()
 

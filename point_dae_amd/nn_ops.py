@@ -437,7 +437,7 @@ def rows_gemm(x, w, w_kn=False, bias=None, epi=0, z=None, may_split=False, big_c
         for m0 in range(0, M, rows):
             m1 = min(M, m0 + rows)
             cfg, _, _ = _lib.rows_gemm_plan(m1 - m0, N, K, w_kn, False)
-            if big_cfg is not None and cfg < 16 and BIG_TILES and m1 - m0 >= BIG_ROWS:
+            if big_cfg is not None and cfg < 16 and m1 - m0 >= BIG_ROWS:
                 cfg = big_cfg
             rows_c = m1 - m0
             probed_family('rows_gemm', 2.0 * rows_c * N * K,
@@ -447,7 +447,7 @@ def rows_gemm(x, w, w_kn=False, bias=None, epi=0, z=None, may_split=False, big_c
                           nbytes=4.0 * (rows_c * K + N * K + rows_c * N + (rows_c * N if z is not None else 0)))
         return y
     cfg, splits, sb = _lib.rows_gemm_plan(M, N, K, w_kn, may_split)
-    if big_cfg is not None and cfg < 16 and M >= BIG_ROWS and splits == 1 and BIG_TILES:
+    if big_cfg is not None and cfg < 16 and M >= BIG_ROWS and splits == 1:
         cfg = big_cfg         # a caller's measured fp32-input tile shape for a multi-millisecond product (that plan is calibrated
                               # on M <= 8192; the exact-split family's plan, cfg >= 16, prices rounds and stands)
     y = _empty((splits, M, N) if splits > 1 else (M, N), x)
@@ -461,7 +461,6 @@ def rows_gemm(x, w, w_kn=False, bias=None, epi=0, z=None, may_split=False, big_c
 # Tile shapes for the FoldingNet stage's multi-millisecond products (tools/lab/rows_big.py, 524288 x 512 x 512: bias+ReLU
 # forward 96x128 tiles 126.7 vs 121.9 TFLOP/s on 64x64; ReLU-masked data gradient 128x128 123.0 vs 115.7)
 BIG_ROWS = 1 << 19                 # (the published variant's 190 k-row stages are faster on the planned 64x64 tiles: 17.55 vs 17.63 ms)
-BIG_TILES = os.environ.get('PDAE_BIG_TILES', '1') != '0'
 
 
 # Gradient sink.  FlatDataParallel tags every parameter it owns with (weakref to itself, index); a graphed step
@@ -491,39 +490,14 @@ def _sink_views(tags, weights):
     return owner, idx, [owner.grad_views[i] for i in idx]
 
 
-# lab switch (tools/lab/ab.sh): one grouped launch per block instead of one per stack (measured 0.3 ms slower)
-WGRAD_PER_BLOCK = os.environ.get('PDAE_WGRAD_PER_BLOCK', '0') != '0'
-# blocks per grouped weight-gradient launch (0 = a whole stack): a launch's operands are the activations / gradients of
-# its blocks' backward passes, and a group small enough to still sit in the 256 MB Infinity Cache is read from there
-WGRAD_GROUP = int(os.environ.get('PDAE_WGRAD_GROUP', '0'))
-
-
 def flush_wgrad_queue(owner):
-    """Issue the queued weight gradients of an armed FlatDataParallel (see _TransformerBlock.backward).
-    With `owner.wgrad_stream` set (graph_step: PDAE_WGRAD_SIDE=1) the launch goes to that side stream behind an event
-    on the current one -- a parallel branch of the captured graph: nothing downstream of the backward reads a weight
-    gradient, so the stack's ~1 ms of dW tiles may run beside the rest of the backward (the other stack's / the
-    embedder's chain of small launches); join_wgrad_stream() closes the branch before the gradients are gathered."""
+    """Issue the queued weight gradients of an armed FlatDataParallel (see _TransformerBlock.backward)."""
     q = owner.wgrad_queue
     if q:
         flops = 2.0 * sum(dy.shape[0] * dy.shape[1] * x.shape[1] for dy, x, _, _ in q)
-        side = getattr(owner, 'wgrad_stream', None)
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                _lib.rows_wgrad_multi(q)
-            owner.wgrad_inflight.append(q)           # operands stay alive until the join
-        else:
-            probed_family('rows_wgrad', flops, lambda: _lib.rows_wgrad_multi(q),
-                          nbytes=4.0 * sum(dy.shape[0] * (dy.shape[1] + x.shape[1]) + dy.shape[1] * x.shape[1] for dy, x, _, _ in q))
+        probed_family('rows_wgrad', flops, lambda: _lib.rows_wgrad_multi(q),
+                      nbytes=4.0 * sum(dy.shape[0] * (dy.shape[1] + x.shape[1]) + dy.shape[1] * x.shape[1] for dy, x, _, _ in q))
         owner.wgrad_queue = []
-
-
-def join_wgrad_stream(owner):
-    side = getattr(owner, 'wgrad_stream', None)
-    if side is not None and owner.wgrad_inflight:
-        torch.cuda.current_stream().wait_stream(side)
-        owner.wgrad_inflight = []
 
 
 def rows_wgrad(dys, xs, with_bias, outs=None, db_outs=None):
@@ -1053,7 +1027,7 @@ class _TransformerBlock(torch.autograd.Function):
                                   (da2, h, views[3], None)]
             owner.sink_written.update(sink[1])
             first_of_stack = ctx.pos_grad is None or ctx.pos_grad[1] == 0
-            if first_of_stack or WGRAD_PER_BLOCK or (WGRAD_GROUP and len(owner.wgrad_queue) >= 4 * WGRAD_GROUP):
+            if first_of_stack:
                 flush_wgrad_queue(owner)
             dwqkv = dwproj = dw1 = dw2 = dbf1 = None
         elif tail:                             # two row counts: two groups

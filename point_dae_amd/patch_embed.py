@@ -35,9 +35,6 @@ from .arena import arena
 from .probe import probed, probed_family
 
 
-ALGEBRA = os.environ.get('PDAE_EMBED_ALGEBRA', '1') != '0'
-
-
 def _empty(shape, like, dtype=torch.float32):
     return torch.empty(shape, device=like.device, dtype=dtype)
 
@@ -63,7 +60,6 @@ def _gemm(x, w, w_kn=False, bias=None):
 
 # (A/B: 0 = the small element-wise steps of the embedder as framework launches: 2 + 4 + 3 + 2 of them instead of 1 + 1 + 1 + 1)
 GLUE = os.environ.get('PDAE_EMBED_GLUE', os.environ.get('PDAE_GLUE', '1')) != '0'
-BN_FUSED = os.environ.get('PDAE_BN_FUSED', '1') != '0'     # (A/B: 0 = the data gradient and BatchNorm's sums as two launches)
 
 
 def _gemm_bnstats(dy, w, X, groups, sc, sh, mean, invstd):
@@ -74,7 +70,7 @@ def _gemm_bnstats(dy, w, X, groups, sc, sh, mean, invstd):
     N = w.shape[1]
     t = _empty((M, N), dy)
     S = _empty((2, N), dy)
-    ws = _empty((max(_lib.lib().pdae_rows_gemm_bnrelu_stats_workspace(M, N), 1),), dy) if BN_FUSED else None
+    ws = _empty((max(_lib.lib().pdae_rows_gemm_bnrelu_stats_workspace(M, N), 1),), dy)
     probed_family('rows_gemm', 2.0 * M * N * K,
                   lambda: _lib.call('pdae_rows_gemm_bnrelu_stats', dy, M, N, K, _lib.ptr(dy), _lib.ptr(w), _lib.ptr(X),
                                     _lib.ptr(groups), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(mean), _lib.ptr(invstd),
@@ -84,8 +80,7 @@ def _gemm_bnstats(dy, w, X, groups, sc, sh, mean, invstd):
 
 
 # the embedder's own weight gradients (group-listed operands, BatchNorm + ReLU recomputed) on the grouped kernel of
-# csrc/rows_gemm.hip (ordered reduction, no atomics, no memset); PDAE_EMBED_WGRAD=tn: round 1's gemm_tn kernels (A/B)
-WGRAD_ROWS = os.environ.get('PDAE_EMBED_WGRAD', 'rows') != 'tn'
+# csrc/rows_gemm.hip (ordered reduction, no atomics, no memset)
 DEBUG_KEEP = None       # (lab) a dict: the backward keeps clones of its intermediates in it (tools/lab/model_nondet.py)
 
 
@@ -94,19 +89,11 @@ def _wgrad_listed(M, dy, a_groups, x, b_groups, scale=None, shift=None, bias=Fal
     N, K = dy.shape[1], x.shape[1]
     dw = _empty((N, K), x)
     db = _empty((N,), x) if bias else None
-    if WGRAD_ROWS:
-        ws = _empty((max(_lib.rows_wgrad_workspace(M, [N], [K]), 1),), x)
-        probed_family('rows_wgrad', 2.0 * M * N * K,
-                      lambda: _lib.call('pdae_rows_wgrad_listed', x, M, N, K, _lib.ptr(dy), _lib.ptr(a_groups), _lib.ptr(x),
-                                        _lib.ptr(b_groups), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(dw), _lib.ptr(db),
-                                        _lib.ptr(ws)), nbytes=4.0 * (M * (N + K) + N * K))
-    elif scale is not None:
-        assert a_groups is None
-        _lib.call('pdae_bnrelu_linear_backward_weight', x, M, N, K, _lib.ptr(dy), _lib.ptr(x), _lib.ptr(scale),
-                  _lib.ptr(shift), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(b_groups))
-    else:
-        _lib.call('pdae_linear_backward_weight_listed', x, M, N, K, _lib.ptr(dy), _lib.ptr(a_groups), _lib.ptr(x),
-                  _lib.ptr(b_groups), _lib.ptr(dw), _lib.ptr(db))
+    ws = _empty((max(_lib.rows_wgrad_workspace(M, [N], [K]), 1),), x)
+    probed_family('rows_wgrad', 2.0 * M * N * K,
+                  lambda: _lib.call('pdae_rows_wgrad_listed', x, M, N, K, _lib.ptr(dy), _lib.ptr(a_groups), _lib.ptr(x),
+                                    _lib.ptr(b_groups), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(dw), _lib.ptr(db),
+                                    _lib.ptr(ws)), nbytes=4.0 * (M * (N + K) + N * K))
     return dw, db
 
 
@@ -212,7 +199,7 @@ class PatchEmbedFunction(torch.autograd.Function):
         # conv4: BN2+ReLU producer, only the group max leaves the kernel.  It comes after the
         # last BatchNorm, so it is evaluated only for the groups whose tokens are used
         # (`groups`: the visible patches; masked tokens are discarded by the caller).
-        algebra = ALGEBRA and groups is not None and masked is not None and masked.numel() > 0 and training
+        algebra = groups is not None and masked is not None and masked.numel() > 0 and training
         if groups is not None:
             Gv = groups.numel()
             inv = None

@@ -19,7 +19,6 @@ once per coarse point and once per cloud and added by broadcasting -- the same
 sum, 25.9 -> 8.7 GFLOP per cloud.
 """
 import itertools
-import os
 
 import numpy as np
 import torch
@@ -98,9 +97,6 @@ class _GroupRows(torch.autograd.Function):
         return None, None, None, dfeat
 
 
-GROUP_FUSED = os.environ.get('PDAE_SA_GROUP', 'fused') != 'torch'      # (A/B: the index_select / cat form)
-
-
 class PointnetSAModule(nn.Module):
     """FPS -> ball query -> group (centre-subtracted xyz || features) -> shared MLP -> max."""
 
@@ -120,10 +116,10 @@ class PointnetSAModule(nn.Module):
                 _, new_xyz = furthest_point_sample_with_centres(xyz, self.npoint)
                 idx = ball_query(self.radius, self.nsample, xyz, new_xyz)          # (B,np,ns) i32
             C = 0 if features is None else features.shape[1]
-            if (GROUP_FUSED and C % 4 == 0 and C <= 1024 and N <= 4096 and
+            if (C % 4 == 0 and C <= 1024 and N <= 4096 and
                     4 * (2 * N + 1 + self.npoint * self.nsample) <= 150 * 1024):     # (a cloud's sort lives in LDS)
                 g = _GroupRows.apply(xyz, new_xyz, idx, features)      # xyz - centre | 0 | features: K a multiple of 4
-            else:
+            else:                # shapes the fused kernel refuses: the index_select / cat form
                 flat = (idx.long() + torch.arange(B, device=xyz.device).view(B, 1, 1) * N).reshape(-1)
                 g = xyz.reshape(B * N, 3).index_select(0, flat).reshape(B, self.npoint, self.nsample, 3)
                 g = (g - new_xyz.unsqueeze(2)).reshape(-1, 3)

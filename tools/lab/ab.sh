@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of one environment switch on the default bench, interleaved rounds in separate processes on ONE box:
-#   bash tools/lab/ab.sh PDAE_WGRAD_SIDE 0 1
+#   bash tools/lab/ab.sh PDAE_GLUE 0 1
 cd "$GRAFT_REPO_ROOT"
 VAR=$1; A=$2; B=$3; ROUNDS=${ROUNDS:-2}
 for round in $(seq 1 $ROUNDS); do

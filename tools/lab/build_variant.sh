@@ -1,6 +1,6 @@
 #!/bin/bash
 # lab build (never shipped): the whole library with extra flags -> tools/lab/lab_<name>.so, for PDAE_LIB A/B runs
-#   bash tools/lab/build_variant.sh sc1 "-DR3_SC1"       then on the box:  PDAE_LIB=tools/lab/lab_sc1.so python bench.py ...
+#   bash tools/lab/build_variant.sh plain "-DPDAE_PLAIN_STORES"   then on the box:  PDAE_LIB=tools/lab/lab_plain.so python bench.py ...
 set -e
 cd "$(dirname "$0")/../.."
 NAME=$1; EXTRA=$2

@@ -1,6 +1,6 @@
 #!/bin/bash
-# (lab) which exact-split kernel family in the OTHER process disturbs a process's small reductions?  Process A always runs
-# the fp32-input kernels; process B runs: everything exact-split | only the row GEMMs | only the weight gradients | fp32.
+# (lab) does the exact-split arithmetic in the OTHER process disturb a process's small reductions?  Process A always runs
+# the fp32-input kernels; process B runs: everything exact-split | fp32.
 cd "$GRAFT_REPO_ROOT"
 run() {
   echo "--- B: $1"
@@ -9,6 +9,4 @@ run() {
   wait
 }
 run bf16x3_all "PDAE_X=0"
-run bf16x3_rows_only "PDAE_GEMM_ONLY=rows"
-run bf16x3_wgrad_only "PDAE_GEMM_ONLY=wgrad"
 run f32 "PDAE_GEMM=f32mfma"
