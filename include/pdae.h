@@ -952,6 +952,19 @@ int pdae_adamw_step_gscale(long long n, float* param, const float* grad,
  *                       rows whose first maximal logit is the label (float).  K <= 64,
  *                       B <= 4096.  A label outside [0, K) makes the loss NaN.
  *                       _grad: dlogits = (softmax - onehot) * (*dloss) / B.
+ *   bn_lrelu_dropout    out = Dropout(p)(LeakyReLU(negative_slope)(BatchNorm1d(y))),
+ *                       bn_relu_dropout's contract otherwise (training / eval, the
+ *                       running estimates, u NULL = no dropout, _grad in one launch;
+ *                       training mode with B < 2 is refused).  0 <= negative_slope
+ *                       < 1; slope 0 gives bn_relu_dropout's bits.  The _grad's
+ *                       LeakyReLU test recomputes the forward's pre-activation.
+ *   softmax_xent_smooth the label-smoothed cross-entropy of DGCNN's smoothloss
+ *                       (models/PointCAE_DGCNN.py:592-600): target t = onehot (1-eps)
+ *                       + (1-onehot) eps/(K-1), loss_r = lse_r - sum_k t_k x_k, mean
+ *                       over the rows added in row order; *correct as softmax_xent.
+ *                       2 <= K <= 64, B <= 4096, 0 <= eps <= 1; eps 0 gives
+ *                       softmax_xent's bits.  A label outside [0, K) makes the loss
+ *                       NaN.  _grad: dlogits = (softmax - t) * (*dloss) / B.
  *   grad_norm_clip      the L2 norm of grad (n floats, 16-byte aligned) as
  *                       grad_norm_parts(n) fp64 per-block partials (caller's
  *                       workspace) added in block order: *norm (nullable) and *coef =
@@ -973,6 +986,17 @@ int pdae_softmax_xent(int B, int K, const float* logits, const int64_t* labels, 
                       pdae_stream_t stream);
 int pdae_softmax_xent_grad(int B, int K, const float* logits, const int64_t* labels, const float* dloss,
                            float* dlogits, pdae_stream_t stream);
+int pdae_bn_lrelu_dropout(int B, int N, const float* y, const float* gamma, const float* beta, float eps,
+                          float momentum, float* running_mean /*nullable*/, float* running_var /*nullable*/,
+                          long long* num_batches_tracked /*nullable*/, int training, float negative_slope, float p,
+                          const float* u /*nullable*/, float* out, float* mean, float* invstd, pdae_stream_t stream);
+int pdae_bn_lrelu_dropout_grad(int B, int N, const float* y, const float* gamma, const float* beta, const float* mean,
+                               const float* invstd, float negative_slope, float p, const float* u /*nullable*/,
+                               const float* dout, float* dy, float* dgamma, float* dbeta, pdae_stream_t stream);
+int pdae_softmax_xent_smooth(int B, int K, float eps, const float* logits, const int64_t* labels, float* loss,
+                             float* correct, pdae_stream_t stream);
+int pdae_softmax_xent_smooth_grad(int B, int K, float eps, const float* logits, const int64_t* labels,
+                                  const float* dloss, float* dlogits, pdae_stream_t stream);
 int pdae_grad_norm_parts(long long n);
 int pdae_grad_norm_clip(long long n, const float* grad, float max_norm, double* partials, float* norm /*nullable*/,
                         float* coef, pdae_stream_t stream);

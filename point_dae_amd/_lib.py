@@ -137,6 +137,10 @@ _SIGNATURES = {
     "pdae_softmax_xent": [_i, _i, _vp, _vp, _vp, _vp, _vp],
     "pdae_softmax_xent_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp],
     "pdae_grad_norm_clip": [ctypes.c_longlong, _vp, _f, _vp, _vp, _vp, _vp],
+    "pdae_bn_lrelu_dropout": [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp],
+    "pdae_bn_lrelu_dropout_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_softmax_xent_smooth": [_i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "pdae_softmax_xent_smooth_grad": [_i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "pdae_calib_mfma_bf16": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_calib_copy": [ctypes.c_longlong, _vp, _vp, _vp],
 }

@@ -7,6 +7,11 @@
 //                                 Linear: batch statistics, running estimates, the affine, ReLU and the dropout mask in
 //                                 ONE launch (a thread owns a column and walks the B rows), backward likewise
 //   pdae_softmax_xent / _grad     nn.CrossEntropyLoss() (mean) + the argmax hit count (get_loss_acc, :634-638)
+//   pdae_bn_lrelu_dropout / _grad the same for DGCNN's head (models/PointCAE_DGCNN.py:572-663): BatchNorm1d ->
+//                                 LeakyReLU(slope) -> Dropout(p), a sibling of bn_relu_dropout (whose kernels stay as
+//                                 they are); at slope 0 it gives bn_relu_dropout's bits
+//   pdae_softmax_xent_smooth / _grad  DGCNN's smoothloss (get_loss_acc, :592-600): cross-entropy against the target
+//                                 t = onehot (1 - eps) + (1 - onehot) eps / (K - 1), + the same hit count
 //   pdae_grad_norm_clip           torch.nn.utils.clip_grad_norm_ (runner_finetune.py:201-202) on the flat gradient
 //                                 buffer: per-block fp64 partials, then one block adds them in block order; the
 //                                 clip coefficient stays on the device (AdamW reads it: pdae_adamw_step_gscale)
@@ -157,6 +162,85 @@ __global__ __launch_bounds__(256) void bn_relu_dropout_grad_kernel(int B, int N,
   }
 }
 
+// bn_relu_dropout_kernel with LeakyReLU: act(v) = max(v, 0) + slope min(v, 0) -- one of the two terms is 0, so it is
+// torch's `v > 0 ? v : v * slope` with a +0 (never -0) for v <= 0 at slope 0, as fmaxf(v, 0) gives
+__global__ __launch_bounds__(256) void bn_lrelu_dropout_kernel(int B, int N, const float* __restrict__ y,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               float eps, float momentum, float* __restrict__ rmean,
+                                                               float* __restrict__ rvar, long long* __restrict__ counter,
+                                                               int training, float slope, float p,
+                                                               const float* __restrict__ u, float* __restrict__ out,
+                                                               float* __restrict__ mean, float* __restrict__ invstd) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (training && n == 0 && counter) *counter += 1;
+  if (n >= N) return;
+  float m, is;
+  if (training) {
+    double s1 = 0.0;
+    for (int r = 0; r < B; ++r) s1 += (double)y[(size_t)r * N + n];
+    const double mu = s1 / B;
+    double s2 = 0.0;
+    for (int r = 0; r < B; ++r) {
+      const double d = (double)y[(size_t)r * N + n] - mu;
+      s2 += d * d;
+    }
+    const double var = s2 / B;
+    m = (float)mu;
+    is = 1.0f / sqrtf((float)var + eps);
+    if (rmean) rmean[n] = (1.0f - momentum) * rmean[n] + momentum * m;
+    if (rvar) rvar[n] = (1.0f - momentum) * rvar[n] + momentum * (float)(s2 / (B - 1));
+    mean[n] = m;
+    invstd[n] = is;
+  } else {
+    m = rmean[n];
+    is = 1.0f / sqrtf(rvar[n] + eps);
+  }
+  const float sc = gamma[n] * is, be = beta[n];
+  const float keep_scale = 1.0f / (1.0f - p);
+  for (int r = 0; r < B; ++r) {
+    const size_t k = (size_t)r * N + n;
+    const float z = (y[k] - m) * sc + be;
+    float v = fmaxf(z, 0.f) + slope * fminf(z, 0.f);
+    if (u) v = u[k] >= p ? v * keep_scale : 0.f;
+    out[k] = v;
+  }
+}
+
+// backward of bn_lrelu_dropout_kernel (training mode), bn_relu_dropout_grad_kernel's arithmetic with the LeakyReLU
+// derivative: g = dout * dropout mask * (z > 0 ? 1 : slope), z recomputed as the forward computes it.  `+ 0.f` turns
+// slope * dout = -0 into +0, so that slope 0 gives bn_relu_dropout_grad's bits
+__global__ __launch_bounds__(256) void bn_lrelu_dropout_grad_kernel(int B, int N, const float* __restrict__ y,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                    const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                    float slope, float p, const float* __restrict__ u,
+                                                                    const float* __restrict__ dout, float* __restrict__ dy,
+                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const float m = mean[n], is = invstd[n], ga = gamma[n];
+  const float sc = ga * is, be = beta[n];
+  const float keep_scale = 1.0f / (1.0f - p);
+  double sg = 0.0, sgx = 0.0;
+  for (int r = 0; r < B; ++r) {
+    const size_t k = (size_t)r * N + n;
+    const float x = y[k];
+    float g = (x - m) * sc + be > 0.f ? dout[k] : slope * dout[k] + 0.f;
+    if (u) g = u[k] >= p ? g * keep_scale : 0.f;
+    sg += (double)g;
+    sgx += (double)g * (double)((x - m) * is);
+  }
+  dbeta[n] = (float)sg;
+  dgamma[n] = (float)sgx;
+  const float c1 = (float)(sg / B), c2 = (float)(sgx / B);
+  for (int r = 0; r < B; ++r) {
+    const size_t k = (size_t)r * N + n;
+    const float x = y[k];
+    float g = (x - m) * sc + be > 0.f ? dout[k] : slope * dout[k] + 0.f;
+    if (u) g = u[k] >= p ? g * keep_scale : 0.f;
+    dy[k] = sc * (g - c1 - (x - m) * is * c2);
+  }
+}
+
 __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
@@ -212,6 +296,56 @@ __global__ __launch_bounds__(256) void softmax_xent_grad_kernel(int B, int K, co
   const float s = wave_sum(e);
   const float scale = *dloss / (float)B;
   if (lane < K) dlogits[(size_t)r * K + lane] = (e / s - (labels[r] == lane ? 1.f : 0.f)) * scale;
+}
+
+// softmax_xent_kernel against the smoothed target t_k = k == label ? 1 - eps : eps / (K - 1):
+// loss_r = lse - sum_k t_k x_k (the lane products added by the wave's butterfly); the hit count as softmax_xent.
+// At eps = 0 the sum is x[label] plus zeros: softmax_xent's bits
+__global__ __launch_bounds__(256) void softmax_xent_smooth_kernel(int B, int K, float on, float off,
+                                                                  const float* __restrict__ logits,
+                                                                  const int64_t* __restrict__ labels,
+                                                                  float* __restrict__ loss, float* __restrict__ correct) {
+  __shared__ float rl[XENT_MAX_B];
+  __shared__ unsigned char rh[XENT_MAX_B];
+  const int lane = lane_id(), w = threadIdx.x / kWave;
+  for (int r = w; r < B; r += 4) {
+    const float x = lane < K ? logits[(size_t)r * K + lane] : -INFINITY;
+    const float mx = wave_max(x);
+    const float s = wave_sum(lane < K ? expf(x - mx) : 0.f);
+    const int64_t lab = labels[r];
+    const bool ok = lab >= 0 && lab < K;
+    const float tx = wave_sum(lane < K ? (lane == lab ? on : off) * x : 0.f);
+    const unsigned long long at = __ballot(lane < K && x == mx);
+    const int am = __ffsll((long long)at) - 1;
+    if (lane == 0) {
+      rl[r] = ok ? (mx + logf(s)) - tx : NAN;
+      rh[r] = ok && am == lab;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f, h = 0.f;
+    for (int r = 0; r < B; ++r) t += rl[r], h += rh[r];
+    *loss = t / B;
+    *correct = h;
+  }
+}
+
+// dlogits[r][k] = (softmax(x_r)[k] - t_k) * dloss / B, one wave per row
+__global__ __launch_bounds__(256) void softmax_xent_smooth_grad_kernel(int B, int K, float on, float off,
+                                                                       const float* __restrict__ logits,
+                                                                       const int64_t* __restrict__ labels,
+                                                                       const float* __restrict__ dloss,
+                                                                       float* __restrict__ dlogits) {
+  const int lane = lane_id();
+  const int r = blockIdx.x * 4 + threadIdx.x / kWave;
+  if (r >= B) return;
+  const float x = lane < K ? logits[(size_t)r * K + lane] : -INFINITY;
+  const float mx = wave_max(x);
+  const float e = lane < K ? expf(x - mx) : 0.f;
+  const float s = wave_sum(e);
+  const float scale = *dloss / (float)B;
+  if (lane < K) dlogits[(size_t)r * K + lane] = (e / s - (labels[r] == lane ? on : off)) * scale;
 }
 
 // per-block partial sums of squares of g (float4 grid-stride; each thread adds its squares in fp32 groups of 4, the
@@ -339,6 +473,42 @@ extern "C" int pdae_bn_relu_dropout_grad(int B, int N, const float* y, const flo
   return check_launch("bn_relu_dropout_grad");
 }
 
+extern "C" int pdae_bn_lrelu_dropout(int B, int N, const float* y, const float* gamma, const float* beta, float eps,
+                                     float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
+                                     int training, float negative_slope, float p, const float* u, float* out, float* mean,
+                                     float* invstd, pdae_stream_t stream) {
+  if (B < 1 || N < 1) return bad_arg("bn_lrelu_dropout: B >= 1 and N >= 1 required");
+  if (!y || !gamma || !beta || !out) return bad_arg("bn_lrelu_dropout: null pointer");
+  if (!(negative_slope >= 0.f && negative_slope < 1.f)) return bad_arg("bn_lrelu_dropout: 0 <= negative_slope < 1 required");
+  if (training) {
+    if (B < 2) return bad_arg("bn_lrelu_dropout: training-mode batch statistics need B >= 2");
+    if (!mean || !invstd) return bad_arg("bn_lrelu_dropout: training mode writes mean and invstd");
+    if (!(p >= 0.f && p < 1.f)) return bad_arg("bn_lrelu_dropout: 0 <= p < 1 required");
+  } else {
+    if (!running_mean || !running_var) return bad_arg("bn_lrelu_dropout: eval mode reads the running estimates");
+    u = nullptr;
+  }
+  hipLaunchKernelGGL(bn_lrelu_dropout_kernel, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y, gamma, beta,
+                     eps, momentum, running_mean, running_var, num_batches_tracked, training, negative_slope, p, u, out, mean,
+                     invstd);
+  return check_launch("bn_lrelu_dropout");
+}
+
+extern "C" int pdae_bn_lrelu_dropout_grad(int B, int N, const float* y, const float* gamma, const float* beta,
+                                          const float* mean, const float* invstd, float negative_slope, float p,
+                                          const float* u, const float* dout, float* dy, float* dgamma, float* dbeta,
+                                          pdae_stream_t stream) {
+  if (B < 2 || N < 1) return bad_arg("bn_lrelu_dropout_grad: B >= 2 and N >= 1 required");
+  if (!(negative_slope >= 0.f && negative_slope < 1.f))
+    return bad_arg("bn_lrelu_dropout_grad: 0 <= negative_slope < 1 required");
+  if (!(p >= 0.f && p < 1.f)) return bad_arg("bn_lrelu_dropout_grad: 0 <= p < 1 required");
+  if (!y || !gamma || !beta || !mean || !invstd || !dout || !dy || !dgamma || !dbeta)
+    return bad_arg("bn_lrelu_dropout_grad: null pointer");
+  hipLaunchKernelGGL(bn_lrelu_dropout_grad_kernel, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y, gamma,
+                     beta, mean, invstd, negative_slope, p, u, dout, dy, dgamma, dbeta);
+  return check_launch("bn_lrelu_dropout_grad");
+}
+
 extern "C" int pdae_softmax_xent(int B, int K, const float* logits, const int64_t* labels, float* loss, float* correct,
                                  pdae_stream_t stream) {
   if (B < 1 || K < 1) return bad_arg("softmax_xent: B >= 1 and K >= 1 required");
@@ -356,6 +526,40 @@ extern "C" int pdae_softmax_xent_grad(int B, int K, const float* logits, const i
   hipLaunchKernelGGL(softmax_xent_grad_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), B, K, logits, labels, dloss,
                      dlogits);
   return check_launch("softmax_xent_grad");
+}
+
+// the target's two values as the reference forms them in fp32: one_hot * (1 - eps) + (1 - one_hot) * eps / (K - 1)
+static int smooth_target(const char* what, int B, int K, float eps, float* on, float* off) {
+  if (B < 1 || K < 2) return bad_arg(what);
+  if (K > kWave || B > XENT_MAX_B) return unsupported(what);
+  if (!(eps >= 0.f && eps <= 1.f)) return bad_arg(what);
+  *on = 1.0f - eps;
+  *off = eps / (float)(K - 1);
+  return PDAE_OK;
+}
+
+extern "C" int pdae_softmax_xent_smooth(int B, int K, float eps, const float* logits, const int64_t* labels, float* loss,
+                                        float* correct, pdae_stream_t stream) {
+  float on, off;
+  if (const int st = smooth_target("softmax_xent_smooth: B in [1, 4096], K in [2, 64] and eps in [0, 1] required", B, K,
+                                   eps, &on, &off))
+    return st;
+  if (!logits || !labels || !loss || !correct) return bad_arg("softmax_xent_smooth: null pointer");
+  hipLaunchKernelGGL(softmax_xent_smooth_kernel, dim3(1), dim3(256), 0, as_stream(stream), B, K, on, off, logits, labels,
+                     loss, correct);
+  return check_launch("softmax_xent_smooth");
+}
+
+extern "C" int pdae_softmax_xent_smooth_grad(int B, int K, float eps, const float* logits, const int64_t* labels,
+                                             const float* dloss, float* dlogits, pdae_stream_t stream) {
+  float on, off;
+  if (const int st = smooth_target("softmax_xent_smooth_grad: B in [1, 4096], K in [2, 64] and eps in [0, 1] required", B,
+                                   K, eps, &on, &off))
+    return st;
+  if (!logits || !labels || !dloss || !dlogits) return bad_arg("softmax_xent_smooth_grad: null pointer");
+  hipLaunchKernelGGL(softmax_xent_smooth_grad_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), B, K, on, off,
+                     logits, labels, dloss, dlogits);
+  return check_launch("softmax_xent_smooth_grad");
 }
 
 extern "C" int pdae_grad_norm_parts(long long n) {

@@ -3,7 +3,8 @@
 The fine-tuned classifier (point_transformer.py, models/Point_MAE.py:578-706 of the reference) reuses the pretraining
 step's patch embedder and Transformer blocks; what it adds around them is here: the cls token / cls position in front of
 the group tokens, the cls + max pooling of the final norm's output, the head's BatchNorm1d -> ReLU -> Dropout, the
-softmax cross-entropy with the argmax hit count, and the global gradient-norm clip coefficient.  Every function raises
+softmax cross-entropy with the argmax hit count, and the global gradient-norm clip coefficient.  The DGCNN classifier
+(dgcnn_cls.py) adds the LeakyReLU variant of the head's glue and the label-smoothed cross-entropy.  Every function raises
 off the GPU: there is no CPU path.
 """
 import torch
@@ -72,55 +73,73 @@ def cls_max_concat(x):
 
 
 class _BnReluDropout(torch.autograd.Function):
+    """slope None: pdae_bn_relu_dropout (ReLU); a float: pdae_bn_lrelu_dropout (LeakyReLU with that negative slope)."""
+
     @staticmethod
-    def forward(ctx, y, gamma, beta, bn, training, p, u):
+    def forward(ctx, y, gamma, beta, bn, training, p, u, slope=None):
         B, N = y.shape
         out = _empty((B, N), y)
         mean = invstd = None
         if training:
             mean, invstd = _empty((N,), y), _empty((N,), y)
         track = bn.track_running_stats
-        _lib.call('pdae_bn_relu_dropout', y, B, N, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), float(bn.eps),
+        name, act = ('pdae_bn_relu_dropout', ()) if slope is None else ('pdae_bn_lrelu_dropout', (float(slope),))
+        _lib.call(name, y, B, N, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), float(bn.eps),
                   float(bn.momentum), _lib.ptr(bn.running_mean) if track else None,
                   _lib.ptr(bn.running_var) if track else None,
-                  _lib.ptr(bn.num_batches_tracked) if track else None, int(training), float(p), _lib.ptr(u),
+                  _lib.ptr(bn.num_batches_tracked) if track else None, int(training), *act, float(p), _lib.ptr(u),
                   _lib.ptr(out), _lib.ptr(mean), _lib.ptr(invstd))
         ctx.save_for_backward(y, gamma, beta, mean, invstd, u)
-        ctx.p, ctx.training = p, training
+        ctx.p, ctx.training, ctx.slope = p, training, slope
         return out
 
     @staticmethod
     def backward(ctx, g):
+        what = 'bn_relu_dropout' if ctx.slope is None else 'bn_lrelu_dropout'
         if not ctx.training:
-            raise NotImplementedError('bn_relu_dropout: the backward is implemented for training-mode BatchNorm')
+            raise NotImplementedError(what + ': the backward is implemented for training-mode BatchNorm')
         y, gamma, beta, mean, invstd, u = ctx.saved_tensors
         g = g.contiguous()
         B, N = y.shape
         dy, dgamma, dbeta = _empty((B, N), g), _empty((N,), g), _empty((N,), g)
-        _lib.call('pdae_bn_relu_dropout_grad', g, B, N, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean),
-                  _lib.ptr(invstd), float(ctx.p), _lib.ptr(u), _lib.ptr(g), _lib.ptr(dy), _lib.ptr(dgamma),
+        act = () if ctx.slope is None else (float(ctx.slope),)
+        _lib.call('pdae_%s_grad' % what, g, B, N, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean),
+                  _lib.ptr(invstd), *act, float(ctx.p), _lib.ptr(u), _lib.ptr(g), _lib.ptr(dy), _lib.ptr(dgamma),
                   _lib.ptr(dbeta))
-        return dy, dgamma, dbeta, None, None, None, None
+        return dy, dgamma, dbeta, None, None, None, None, None
+
+
+def _bn_act_dropout(what, y, bn, p, u, keep, slope):
+    _gpu(y, what)
+    if bn.momentum is None:
+        raise NotImplementedError(what + ': cumulative moving average (momentum=None) is not supported')
+    if not bn.affine:
+        raise NotImplementedError(what + ': BatchNorm1d without affine parameters is not supported')
+    if keep is not None:
+        u = keep.to(torch.float32)              # 1.0 >= p keeps, 0.0 < p drops (0 < p < 1)
+    if u is not None:
+        u = _lib.require(u.contiguous(), 'u', dim=2)
+        if tuple(u.shape) != tuple(y.shape):
+            raise ValueError(f'{what}: the draw has shape {tuple(u.shape)}, the activation {tuple(y.shape)}')
+    if not bn.training or p == 0:
+        u = None
+    return _BnReluDropout.apply(_lib.require(y.contiguous(), 'y', dim=2), bn.weight, bn.bias, bn, bn.training, p, u,
+                                slope)
 
 
 def bn_relu_dropout(y, bn, p, u=None, keep=None):
     """Dropout(p)(ReLU(bn(y))) for y (B, N) and an nn.BatchNorm1d `bn` (its mode decides: training-mode batch statistics
     and running-estimate updates, or the running estimates and no dropout).  The dropout draw is `u` (B, N uniforms: an
     element is kept when u >= p) or `keep` (a boolean keep mask, injected by tests); neither = no dropout."""
-    _gpu(y, 'bn_relu_dropout')
-    if bn.momentum is None:
-        raise NotImplementedError('bn_relu_dropout: cumulative moving average (momentum=None) is not supported')
-    if not bn.affine:
-        raise NotImplementedError('bn_relu_dropout: BatchNorm1d without affine parameters is not supported')
-    if keep is not None:
-        u = keep.to(torch.float32)              # 1.0 >= p keeps, 0.0 < p drops (0 < p < 1)
-    if u is not None:
-        u = _lib.require(u.contiguous(), 'u', dim=2)
-        if tuple(u.shape) != tuple(y.shape):
-            raise ValueError(f'bn_relu_dropout: the draw has shape {tuple(u.shape)}, the activation {tuple(y.shape)}')
-    if not bn.training or p == 0:
-        u = None
-    return _BnReluDropout.apply(_lib.require(y.contiguous(), 'y', dim=2), bn.weight, bn.bias, bn, bn.training, p, u)
+    return _bn_act_dropout('bn_relu_dropout', y, bn, p, u, keep, None)
+
+
+def bn_lrelu_dropout(y, bn, p, slope, u=None, keep=None):
+    """Dropout(p)(LeakyReLU(slope)(bn(y))), otherwise as bn_relu_dropout (the head of DGCNN, models/PointCAE_DGCNN.py:
+    579-588; p = 0 for its first block, which has no Dropout).  0 <= slope < 1; slope 0 gives bn_relu_dropout's bits."""
+    if not 0.0 <= float(slope) < 1.0:
+        raise ValueError(f'bn_lrelu_dropout: 0 <= slope < 1 required, got {slope}')
+    return _bn_act_dropout('bn_lrelu_dropout', y, bn, p, u, keep, float(slope))
 
 
 class _SoftmaxXent(torch.autograd.Function):
@@ -151,6 +170,40 @@ def softmax_xent(logits, labels):
     _gpu(logits, 'softmax_xent')
     labels = _lib.require(labels.to(torch.int64).contiguous(), 'labels', torch.int64, dim=1)
     return _SoftmaxXent.apply(_lib.require(logits.contiguous(), 'logits', dim=2), labels)
+
+
+class _SoftmaxXentSmooth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, eps):
+        B, K = logits.shape
+        loss, correct = _empty((), logits), _empty((), logits)
+        _lib.call('pdae_softmax_xent_smooth', logits, B, K, float(eps), _lib.ptr(logits), _lib.ptr(labels),
+                  _lib.ptr(loss), _lib.ptr(correct))
+        ctx.save_for_backward(logits, labels)
+        ctx.eps = eps
+        ctx.mark_non_differentiable(correct)
+        return loss, correct
+
+    @staticmethod
+    def backward(ctx, dloss, _dcorrect):
+        logits, labels = ctx.saved_tensors
+        B, K = logits.shape
+        dloss = dloss.contiguous()
+        dl = _empty((B, K), logits)
+        _lib.call('pdae_softmax_xent_smooth_grad', logits, B, K, float(ctx.eps), _lib.ptr(logits), _lib.ptr(labels),
+                  _lib.ptr(dloss), _lib.ptr(dl))
+        return dl, None, None
+
+
+def softmax_xent_smooth(logits, labels, eps):
+    """The label-smoothed cross-entropy of DGCNN.get_loss_acc with smoothloss (models/PointCAE_DGCNN.py:592-600):
+    -(t * log_softmax(logits)).sum(1).mean() with t = one_hot (1 - eps) + (1 - one_hot) eps / (K - 1), for logits
+    (B, 2 <= K <= 64) and int64 labels in [0, K) -> (loss, correct) as softmax_xent.  eps = 0 gives softmax_xent's bits."""
+    _gpu(logits, 'softmax_xent_smooth')
+    if not 0.0 <= float(eps) <= 1.0:
+        raise ValueError(f'softmax_xent_smooth: 0 <= eps <= 1 required, got {eps}')
+    labels = _lib.require(labels.to(torch.int64).contiguous(), 'labels', torch.int64, dim=1)
+    return _SoftmaxXentSmooth.apply(_lib.require(logits.contiguous(), 'logits', dim=2), labels, float(eps))
 
 
 class GradNormClip:

@@ -1,5 +1,6 @@
 """Times the classification fine-tuning step (point_transformer.PointTransformer on the ModelNet40 fine-tuning config,
-B=32, N=1024, G=64) and prints ONE JSON line:
+B=32, N=1024, G=64; with --model DGCNN dgcnn_cls.DGCNN on cfgs/finetune_modelnet_dgcnn_smooth.yaml) and prints ONE
+JSON line:
 
   graphed / eager   ms per optimisation step (forward, cross-entropy, backward, clip coefficient, AdamW) and clouds/s,
                     HIP events around `--steps` steps after `--warmup` untimed ones; the input batch is resampled in front
@@ -7,8 +8,12 @@ B=32, N=1024, G=64) and prints ONE JSON line:
   grad_norm_clip_us / adamw_step_gscale_us   one launch pair of each over the flat gradient / parameter buffers, HIP
                     events around `--reps` back-to-back calls
   kernels_per_step  device kernels of one eager step (torch.profiler), null where the profiler records none
+  head_loss_us      (DGCNN only) the head and the smoothed loss, forward and backward, on the encoder's (B, 1024)
+                    feature: HIP events around `--reps` eager calls (host-bound: ~30 launches); head_loss_kernels and
+                    head_loss_kernel_us its device kernels and their summed device time, kernel_us_per_step that sum
+                    for the whole eager step
 
-    timeout -k 10 300 python tools/bench_finetune.py [--steps 30 --warmup 10 --reps 50]
+    timeout -k 10 300 python tools/bench_finetune.py [--model DGCNN] [--steps 30 --warmup 10 --reps 50]
 """
 import argparse
 import json
@@ -17,6 +22,24 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+CONFIGS = {'PointTransformer': 'finetune_modelnet_transferring_features.yaml', 'DGCNN': 'finetune_modelnet_dgcnn_smooth.yaml'}
+
+
+def _kernels(fn):
+    """(device kernels fn() launches, their summed device time in us) from torch.profiler, and None or the error's type
+    name; the counts are None where the profiler records no kernel."""
+    import torch
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        ev = [e for e in prof.events() if e.device_type.name == 'CUDA']
+        return (len(ev) or None, round(sum(e.time_range.elapsed_us() for e in ev), 1) if ev else None), None
+    except Exception as e:                           # a profiler without a device tracer
+        return (None, None), type(e).__name__
 
 
 def _events_ms(fn, n):
@@ -36,6 +59,7 @@ def main(argv=None):
     p.add_argument('--warmup', type=int, default=10)
     p.add_argument('--reps', type=int, default=50)
     p.add_argument('--batch', type=int, default=32)
+    p.add_argument('--model', choices=sorted(CONFIGS), default='PointTransformer')
     a = p.parse_args(argv)
     import torch
     from point_dae_amd import builder
@@ -46,7 +70,7 @@ def main(argv=None):
     from point_dae_amd.runner_finetune import resample, train_step
     from point_dae_amd.synthetic import labelled_clouds
 
-    config = cfg_from_yaml_file(os.path.join(ROOT, 'cfgs', 'finetune_modelnet_transferring_features.yaml'))
+    config = cfg_from_yaml_file(os.path.join(ROOT, 'cfgs', CONFIGS[a.model]))
     B, N = a.batch, config.npoints
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
@@ -54,8 +78,12 @@ def main(argv=None):
     x, y = labelled_clouds(B, 2048, seed=0, classes=3)
     pts = resample(torch.from_numpy(x).to(dev), N)
     labels = torch.from_numpy(y).to(dev)
-    out = dict(workload='finetune_modelnet', batch=B, npoints=N, num_group=config.model.num_group,
-               tokens=config.model.num_group + 1, depth=config.model.depth, steps=a.steps, warmup=a.warmup)
+    if a.model == 'PointTransformer':
+        out = dict(workload='finetune_modelnet', batch=B, npoints=N, num_group=config.model.num_group,
+                   tokens=config.model.num_group + 1, depth=config.model.depth, steps=a.steps, warmup=a.warmup)
+    else:
+        out = dict(workload='finetune_modelnet_dgcnn', batch=B, npoints=N, smoothloss=bool(config.model.smoothloss),
+                   steps=a.steps, warmup=a.warmup)
 
     def setup():
         torch.manual_seed(0)
@@ -70,16 +98,25 @@ def main(argv=None):
         train_step(model, opt, clip, pts, labels)
     ms = _events_ms(lambda: train_step(model, opt, clip, pts, labels), a.steps)
     out['eager'] = dict(ms_per_step=round(ms, 4), clouds_per_s=round(B / ms * 1e3, 1))
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            train_step(model, opt, clip, pts, labels)
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if e.device_type.name == 'CUDA')
-        out['kernels_per_step'] = n or None
-    except Exception as e:                           # a profiler without a device tracer
-        out['kernels_per_step'] = None
-        out['kernels_per_step_error'] = type(e).__name__
+    (out['kernels_per_step'], kernel_us), err = _kernels(lambda: train_step(model, opt, clip, pts, labels))
+    if err:
+        out['kernels_per_step_error'] = err
+    if a.model == 'DGCNN':
+        out['kernel_us_per_step'] = kernel_us
+    if a.model == 'DGCNN':
+        net = model.module
+        with torch.no_grad():
+            feat = net.dgcnn_encoder.forward_rows(pts)
+        feat.requires_grad_()
+
+        def head_loss():
+            loss, _ = net.get_loss_acc(net.head(feat), labels)
+            loss.backward()
+        for _ in range(a.warmup):
+            head_loss()
+        out['head_loss_us'] = round(_events_ms(head_loss, a.reps) * 1e3, 2)
+        (out['head_loss_kernels'], out['head_loss_kernel_us']), _ = _kernels(head_loss)
+        model.zero_grad()
 
     model, opt, clip = setup()
     step = GraphedClassifierStep(model, opt, clip, B, N)
