@@ -192,10 +192,26 @@ class Encoder(nn.Module):
 
     def forward(self, point_groups):
         bs, g, n, _ = point_groups.shape
-        f = self.first_conv(point_groups.reshape(bs * g, n, 3).transpose(2, 1))
-        fg = f.max(dim=2, keepdim=True)[0]
-        f = self.second_conv(torch.cat([fg.expand(-1, -1, n), f], dim=1))
-        return f.max(dim=2)[0].reshape(bs, g, self.encoder_channel)
+        f = _conv_bn_relu_conv(self.first_conv, point_groups.reshape(bs * g, n, 3).transpose(2, 1))
+        fg = _pool_points(f).unsqueeze(-1)
+        f = _conv_bn_relu_conv(self.second_conv, torch.cat([fg.expand(-1, -1, n), f], dim=1))
+        return _pool_points(f).reshape(bs, g, self.encoder_channel)
+
+
+def _conv_bn_relu_conv(seq, x):
+    """Conv1d -> BatchNorm1d -> ReLU -> Conv1d; with RELU_AT set (parity tests), the ReLU passes exactly the entries
+    of the given (groups, C, n) boolean mask instead: one mask per ReLU, consumed in order (an Encoder takes two)."""
+    h = seq[1](seq[0](x))
+    h = h * RELU_AT.pop(0).to(h.dtype) if RELU_AT else seq[2](h)
+    return seq[3](h)
+
+
+def _pool_points(f):
+    """Max over the points of (groups, C, n) -> (groups, C); with POOL_AT set (parity tests), at the given winners
+    instead: one (groups, C) index tensor per pool, consumed in order (an Encoder takes two)."""
+    if POOL_AT:
+        return f.gather(2, POOL_AT.pop(0).unsqueeze(-1)).squeeze(-1)
+    return f.max(dim=2)[0]
 
 
 class Mlp(nn.Module):
@@ -480,8 +496,11 @@ class _SharedMLP(nn.Sequential):
 # Parity-test hook (empty by default: the reference's max_pool2d).  A list of (B, C, npoint) int64 winner indices into
 # the nsample axis, consumed one entry per set-abstraction level in forward order: that level then pools by gathering
 # its pre-pool activations at the given winners, and the backward routes the gradient through them -- the product's
-# own winners replayed on this side (tests/test_gpu_model.py).
+# own winners replayed on this side (tests/test_gpu_model.py).  The patch Encoder's two max-pools over a group's points
+# take (groups, C) entries the same way, first then second (_pool_points; tests/test_gpu_finetune.py), and RELU_AT its
+# two BatchNorm-ReLU decisions as (groups, C, n) masks (_conv_bn_relu_conv).
 POOL_AT = []
+RELU_AT = []
 
 
 class SAModule(nn.Module):

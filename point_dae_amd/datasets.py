@@ -506,7 +506,8 @@ class ShapeNet:
 class ModelNet:
     """Labelled clouds for the SVM probe (datasets/ModelNetDataset.py of the reference yields
     (taxonomy, model_id, (points, label))).  No ModelNet40 files ship with the image: labelled synthetic
-    clouds stand in (synthetic.labelled_clouds); `count` clouds, batches of `bs`, resident on the device."""
+    clouds stand in (synthetic.labelled_clouds); `count` clouds, batches of `bs`, resident on the device.  The `train`
+    subset drops a short last batch, as the reference's train loader does (tools/builder.py: drop_last)."""
 
     def __init__(self, config):
         self.npoints = config.get('npoints', 1024)
@@ -533,6 +534,8 @@ class ModelNet:
         self.rng = np.random.default_rng(seed + 17) if self.aug_type else None
 
     def __len__(self):
+        if self.subset == 'train':                       # the reference's train loader: drop_last (tools/builder.py)
+            return self.count // self.bs
         return (self.count + self.bs - 1) // self.bs
 
     def augment(self, x):
@@ -556,6 +559,9 @@ class ModelNet:
         return flush(x, norm_pending, maps)
 
     def __iter__(self):
-        for i in range(0, self.count, self.bs):
+        # a train subset yields only full batches, as the reference's DataLoader(drop_last=True) does; every other
+        # subset yields every cloud, its last batch short
+        end = len(self) * self.bs if self.subset == 'train' else self.count
+        for i in range(0, end, self.bs):
             x = self.x[i:i + self.bs]
             yield 'ModelNet', i, (self.augment(x) if self.aug_type else x, self.y[i:i + self.bs])

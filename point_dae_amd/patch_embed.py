@@ -142,6 +142,12 @@ def _bn_affine(bn, mean, var_biased, rows, training):
     return scale, shift, mean.contiguous(), invstd.contiguous()
 
 
+# Parity-test hook (None in production): called with what decides the embedder's backward -- the BatchNorm-ReLU inputs
+# (rows y1 and h3 with the affine scale / shift: an entry passes where y * sc + sh > 0, as the kernels evaluate it) and
+# the (groups, C) uint8 max-pool winners arg2, arg4 -- so a test can replay those decisions in the CPU oracle.
+DECISION_HOOK = None
+
+
 class PatchEmbedFunction(torch.autograd.Function):
     """points (R,3) + the 12 parameter tensors of Encoder -> tokens (R/32, C)."""
 
@@ -215,6 +221,8 @@ class PatchEmbedFunction(torch.autograd.Function):
         probed_family('embed_gemm', 2.0 * Rv * c4 * c3, lambda: _lib.call(
             'pdae_embed_bnrelu_conv_groupmax', x, Rv, c4, c3, _lib.ptr(h3), _lib.ptr(sc2), _lib.ptr(sh2),
             _lib.ptr(w4m), _lib.ptr(b4), _lib.ptr(tok), _lib.ptr(arg4), _lib.ptr(groups)))
+        if DECISION_HOOK is not None:
+            DECISION_HOOK(dict(y1=y1, sc1=sc1, sh1=sh1, arg2=arg2, h3=h3, sc2=sc2, sh2=sh2, arg4=arg4))
         ctx.save_for_backward(x, y1, sc1, sh1, mean1, is1, f, g, arg2, h3, sc2, sh2, mean2, is2, arg4,
                               w1m, w2m, wg, wl, w4m, g1, g2, groups, inv)
         ctx.training, ctx.wlt = training, wlt

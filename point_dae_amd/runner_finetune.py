@@ -119,7 +119,7 @@ def run_net(args, config, log=print, log_every=20):
     if int(config.get('step_per_update', 1)) != 1:
         raise NotImplementedError('runner_finetune: step_per_update > 1 (gradient accumulation) is not supported')
     best_metrics, metrics = Acc_Metric(best_metric), Acc_Metric(0.)
-    # the step is replayed as a hipGraph (graph_step.GraphedClassifierStep); a short last batch steps eagerly
+    # the step is replayed as a hipGraph (graph_step.GraphedClassifierStep)
     from .graph_step import GraphedClassifierStep
     graphed = GraphedClassifierStep(model, optimizer, clip, bs, config.npoints)
     if rank == 0:
@@ -133,10 +133,7 @@ def run_net(args, config, log=print, log_every=20):
         t0, n = time.time(), 0
         for idx, (_, _, data) in enumerate(train_loader):
             points = resample(data[0], config.npoints)
-            if points.shape[0] == bs:
-                loss, acc = graphed(points, data[1])
-            else:
-                loss, acc = train_step(model, optimizer, clip, points, data[1])
+            loss, acc = graphed(points, data[1])                 # (the train loader yields only full batches)
             acc_sum += torch.stack([loss, acc])
             n += 1
             if (idx + 1) % log_every == 0 or idx + 1 == len(train_loader):

@@ -8,7 +8,8 @@ replaced by the CPU oracle).  What is committed is data only:
                          pretraining checkpoint of this repository's PointCAE_transformer
   finetune_cls_b4.npz    B=4, N=1024, train mode, drop_path_rate 0: inputs, labels, the injected dropout keep masks,
                          logits, loss, acc, sampled gradients of every parameter, the clip_grad_norm_ total norm, the
-                         BatchNorm running statistics after the step, and eval-mode logits of the same clouds
+                         BatchNorm running statistics after the step, eval-mode logits of the same clouds, and the
+                         patch embedder's near-tie decisions of the training forward (near_ties)
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_finetune_fixtures.py
 """
@@ -84,6 +85,25 @@ def layout():
         json.dump(out, f, indent=1)
 
 
+def near_ties(seen, rel=1e-5):
+    """The patch embedder's decisions the reference took within `rel` of its channel's largest |value|: BatchNorm-ReLU
+    inputs that close to zero (flat indices into (groups, C, n) and whether the ReLU passed them) and max-pools whose
+    best two points are that close (flat indices into (groups, C) and the winner the reference's max took)."""
+    out = {}
+    for key in ('bn1', 'bn2'):
+        v = seen[key]
+        near = (v.abs() / v.abs().amax(dim=(0, 2), keepdim=True)).reshape(-1) <= rel
+        idx = near.nonzero().reshape(-1)
+        out['tie/%s/idx' % key], out['tie/%s/on' % key] = idx.numpy(), (v.reshape(-1)[idx] > 0).numpy()
+    for key in ('f1', 'f2'):
+        v = seen[key]
+        top2 = v.topk(2, dim=2).values
+        gap = (top2[..., 0] - top2[..., 1]) / v.abs().amax(dim=(0, 2)).clamp_min(1e-30).view(1, -1)
+        idx = (gap.reshape(-1) <= rel).nonzero().reshape(-1)
+        out['tie/%s/idx' % key], out['tie/%s/win' % key] = idx.numpy(), v.max(dim=2)[1].reshape(-1)[idx].numpy()
+    return out
+
+
 def cls_fixture(name='finetune_cls_b4.npz', B=4, seed=5):
     import models.Point_MAE as M
     from point_dae_amd.synthetic import shapenet_like_clouds
@@ -98,12 +118,19 @@ def cls_fixture(name='finetune_cls_b4.npz', B=4, seed=5):
     head = ref.cls_head_finetune
     head[3] = _InjectedDropout(0.5, torch.from_numpy(keep1))
     head[7] = _InjectedDropout(0.5, torch.from_numpy(keep2))
+    enc, seen = ref.encoder, {}
+    hooks = [mod.register_forward_hook(lambda m, i, o, key=key: seen.update({key: o.detach().clone()}))
+             for key, mod in (('bn1', enc.first_conv[1]), ('f1', enc.first_conv[3]), ('bn2', enc.second_conv[1]),
+                              ('f2', enc.second_conv[3]))]
     logits = ref(torch.from_numpy(pts))
+    for h in hooks:
+        h.remove()
     loss, acc = ref.get_loss_acc(logits, torch.from_numpy(labels))
     loss.backward()
     out = dict(pts=pts, labels=labels, keep1=keep1, keep2=keep2, seed=np.int64(seed),
                overrides=np.array(repr(list(overrides))), logits=logits.detach().numpy(),
                loss=np.float32(loss.item()), acc=np.float32(acc.item()))
+    out.update(near_ties(seen))
     for pname, p in ref.named_parameters():
         g = p.grad if p.grad is not None else torch.zeros_like(p)
         key = 'grad/' + pname

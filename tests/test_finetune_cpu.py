@@ -107,3 +107,19 @@ def test_finetune_config_keeps_reference_values():
     assert list(cfg.dataset.train.others.aug_type) == ['norm', 'scale', 'translate']
     assert list(cfg.dataset.val.others.aug_type) == ['norm']
     assert cfg.dataset.train._base_.NAME == 'ModelNet' and cfg.dataset.train._base_.NUM_CATEGORY == 40
+
+
+@pytest.mark.parametrize('bs', [32, 5])
+def test_modelnet_train_subset_drops_the_short_last_batch(bs):
+    """The reference's train loader is built with drop_last (tools/builder.py): 2 bs + 1 clouds give 2 full batches and
+    len() 2; the test subset keeps every cloud (3 batches, the last one of 1)."""
+    from point_dae_amd.datasets import ModelNet
+    count = 2 * bs + 1
+    train = ModelNet(dict(subset='train', count=count, bs=bs, npoints=64, device='cpu', aug_type=['clean']))
+    sizes = [data[0].shape[0] for _, _, data in train]
+    assert sizes == [bs, bs] and len(train) == 2
+    assert all(data[1].shape[0] == bs for _, _, data in train)
+    test = ModelNet(dict(subset='test', count=count, bs=bs, npoints=64, device='cpu', aug_type=['clean']))
+    sizes = [data[0].shape[0] for _, _, data in test]
+    assert sizes == [bs, bs, 1] and len(test) == 3
+    assert sum(sizes) == count

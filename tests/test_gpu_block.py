@@ -5,6 +5,7 @@ import torch
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
+F32, BF16X3 = 0, 1               # _lib.GEMM_F32MFMA, _lib.GEMM_BF16X3
 
 
 def _close(a, b, tol):
@@ -13,9 +14,32 @@ def _close(a, b, tol):
     assert err <= tol, err
 
 
-@pytest.mark.parametrize('B,T,H', [(128, 23, 6), (64, 64, 6), (8, 13, 6), (5, 32, 2), (3, 100, 6), (2, 128, 6), (7, 1, 3),
-                                   (16, 47, 6), (4, 33, 2), (128, 64, 6), (9, 63, 3)])
-def test_attention_forward_backward(B, T, H):
+_ATTN_SHAPES = [(128, 23, 6), (64, 64, 6), (8, 13, 6), (5, 32, 2), (3, 100, 6), (2, 128, 6), (7, 1, 3), (16, 47, 6),
+                (4, 33, 2), (128, 64, 6), (9, 63, 3),
+                # fine-tuning's T = 65 (num_group + the cls token: a third 32-row wave with one valid query row), the
+                # same single-row last wave at T = 97, and the last length under the 128 limit
+                (32, 65, 6), (3, 97, 6), (2, 127, 6)]
+
+
+def _attn_cases():
+    """Every shape in both GEMM arithmetics, set explicitly: the exact-split one (the default: its ids are the bare
+    shapes) sends the forward at 32 < T <= 64 to csrc/attention3.hip, the fp32-input one keeps csrc/attention.hip."""
+    return ([pytest.param(BF16X3, *s, id='%d-%d-%d' % s) for s in _ATTN_SHAPES] +
+            [pytest.param(F32, *s, id='f32mfma-%d-%d-%d' % s) for s in _ATTN_SHAPES])
+
+
+@pytest.mark.parametrize('arith,B,T,H', _attn_cases())
+def test_attention_forward_backward(arith, B, T, H):
+    from point_dae_amd import _lib
+    before = _lib.gemm_arith()
+    _lib.set_gemm_arith(arith)
+    try:
+        _attention_forward_backward(B, T, H)
+    finally:
+        _lib.set_gemm_arith(before)
+
+
+def _attention_forward_backward(B, T, H):
     from point_dae_amd import nn_ops
     D, scale = 64, 64 ** -0.5
     g = torch.Generator(device='cuda').manual_seed(B * 1000 + T)

@@ -391,9 +391,9 @@ def _autoencoder_ckpt(path):
     torch.save({'base_model': Point_CAE_DGCNN_FCOnly(cfg).state_dict()}, str(path))
 
 
-def _run_main(tmp_path, *extra):
+def _run_main(tmp_path, *extra, config=CFG):
     env = dict(os.environ, PYTHONPATH=ROOT)
-    cmd = ['timeout', '-k', '10', '600', sys.executable, '-m', 'point_dae_amd.main', '--config', CFG, *extra,
+    cmd = ['timeout', '-k', '10', '600', sys.executable, '-m', 'point_dae_amd.main', '--config', config, *extra,
            '--exp_name', 't']
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -420,3 +420,25 @@ def test_finetune_cli_trains_dgcnn_from_scratch(tmp_path):
     assert '[Validation] EPOCH: 0' in out
     assert len(losses) == 1 and all(np.isfinite(losses)), out
     assert list(tmp_path.glob('experiments/*/cfgs/t/ckpt-last.pth'))
+
+
+def test_finetune_cli_epoch_with_a_one_cloud_tail_drops_it(tmp_path):
+    """2 total_bs + 1 training clouds: the train loader drops the one-cloud tail, as the reference's drop_last does (a
+    B = 1 training step would reach bn_lrelu_dropout, which refuses one row in training mode), so the epoch runs its two
+    full batches; validation still scores every test cloud, the last batch of one included."""
+    import yaml
+    with open(CFG) as f:
+        raw = yaml.safe_load(f)
+    count = 2 * raw['total_bs'] + 1
+    for subset in ('train', 'val', 'test'):
+        node = raw['dataset'][subset]
+        node['_base_'] = os.path.join(ROOT, node['_base_'])
+        node['others']['count'] = count
+    cfg = tmp_path / 'tail.yaml'
+    with open(cfg, 'w') as f:
+        yaml.safe_dump(raw, f)
+    out, losses = _run_main(tmp_path, '--scratch_model', '--max_epoch', '0', config=str(cfg))
+    assert '[Epoch 0/0][Batch 2/2]' in out, out
+    assert '[Batch 3/' not in out, out
+    assert len(losses) == 1 and all(np.isfinite(losses)), out
+    assert '[Validation] EPOCH: 0' in out

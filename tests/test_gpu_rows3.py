@@ -3,8 +3,10 @@ the fp32-input MFMA kernels it replaces as the default (the reference runs these
 models/PointCAE_transformer.py:94-158, models/PointCAE_pointnetv2.py:135-173).
 
 Admission gate: on EVERY product of the cfg3, published-variant, cfg2, cfg5 per-GPU (N = 2048, G = 128, B = 32) and
-DGCNN optimisation steps (tests/golden/gemm_shapes.json, recorded at the C boundary by tools/dump_gemm_shapes.py), each
-run at the step's own row count, the error against an fp64 product is at or below the fp32-input MFMA kernel's on the
+DGCNN optimisation steps, and of the two ModelNet40 fine-tuning classifiers' steps and validation forwards
+(PointTransformer at T = 65: M = 2080 trunk rows, 260 at the B = 4 last test batch, M = 32 / 4 head products; DGCNN)
+(tests/golden/gemm_shapes.json, recorded at the C boundary by tools/dump_gemm_shapes.py), each run at the step's own
+row count, the error against an fp64 product is at or below the fp32-input MFMA kernel's on the
 same inputs.  Two statistics of |C - C64| / max |C64|: the RMS over the
 output (stable: measured ratio exact-split / fp32-input 0.5-0.65 on the row GEMMs) must not exceed the fp32-input
 kernel's; the MAXIMUM (an extreme value of ~1e6 samples: +-30 % from seed to seed for either kernel, tools/lab notes in

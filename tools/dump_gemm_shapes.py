@@ -1,7 +1,10 @@
 """Every distinct product the row-GEMM family computes in one optimisation step of cfg3 (PointCAE_transformer, B = 128,
 all visible-token counts the mask ratio can draw), the published variant, cfg2 (Point_CAE_PointNetv2, B = 128), the cfg5
-per-GPU shape (N = 2048, G = 128, B = 32: 20 drawn visible-token counts and both ends, 26 and 64) and DGCNN
-(Point_CAE_DGCNN_FCOnly on the cfg2 YAML, B = 32): recorded at the C boundary (point_dae_amd/_lib.CALL_HOOK) while the
+per-GPU shape (N = 2048, G = 128, B = 32: 20 drawn visible-token counts and both ends, 26 and 64), DGCNN
+(Point_CAE_DGCNN_FCOnly on the cfg2 YAML, B = 32) and the two ModelNet40 fine-tuning classifiers, ft_transformer
+(PointTransformer, T = 65 tokens: trunk products of M = 65 B rows) and ft_dgcnn (DGCNN with the smoothed loss), each at
+total_bs = 32: one eager training step (forward, loss, backward) and eval-mode forwards at B = 32 and at B = 4, the
+short last batch of ModelNet40's 2468 test clouds.  Recorded at the C boundary (point_dae_amd/_lib.CALL_HOOK) while the
 steps run eagerly -> tests/golden/gemm_shapes.json, the shape list of tests/test_gpu_rows3.py.  Run on a GPU:
 python tools/dump_gemm_shapes.py"""
 import json
@@ -16,6 +19,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from point_dae_amd import _lib  # noqa: E402
+
+FT_TRANSFORMER = 'cfgs/finetune_modelnet_transferring_features.yaml'
+FT_DGCNN = 'cfgs/finetune_modelnet_dgcnn_smooth.yaml'
+FT_TEST_COUNT = 2468                 # ModelNet40's test clouds: at total_bs = 32 the last batch holds 4
 
 gemm, wgrad = set(), set()
 
@@ -39,7 +46,8 @@ def main():
     from point_dae_amd import builder
     from point_dae_amd.config import cfg_from_yaml_file
     from point_dae_amd.data_parallel import FlatDataParallel
-    from point_dae_amd.graph_step import GraphedStaticStep, GraphedTrainStep, use_created_stream
+    from point_dae_amd.graph_step import (GraphedClassifierStep, GraphedStaticStep, GraphedTrainStep,
+                                          use_created_stream)
     from point_dae_amd.synthetic import shapenet_like_clouds
     device = torch.device('cuda', 0)
     use_created_stream(device)
@@ -88,6 +96,31 @@ def main():
                         step._fwd_bwd(tvis)
                         model.zero_grad()
                 print(wl, 'visible-token counts', sorted(seen), flush=True)
+        _lib.CALL_HOOK = None
+        torch.cuda.synchronize()
+        out[wl] = {'gemm': sorted(gemm), 'wgrad': sorted(wgrad)}
+        print(wl, len(gemm), 'gemm shapes,', len(wgrad), 'wgrad shapes', flush=True)
+        del model, optimizer, step
+        torch.cuda.empty_cache()
+    for wl, cfg in (('ft_transformer', FT_TRANSFORMER), ('ft_dgcnn', FT_DGCNN)):
+        gemm.clear(), wgrad.clear()
+        config = cfg_from_yaml_file(os.path.join(ROOT, cfg))
+        B, N = config.total_bs, config.npoints
+        random.seed(5), np.random.seed(5), torch.manual_seed(5)
+        x = torch.from_numpy(shapenet_like_clouds(B, N, seed=7)).to(device)
+        labels = torch.from_numpy(np.random.default_rng(5).integers(0, config.model.cls_dim, B)).to(device)
+        model = FlatDataParallel(builder.model_builder(config.model).to(device), broadcast=False, process_group=None)
+        model.world_size = 1
+        optimizer, _ = builder.build_opti_sche(model, config)
+        model.train()
+        model.zero_grad()
+        _lib.CALL_HOOK = hook
+        step = GraphedClassifierStep(model, optimizer, None, B, N)
+        step(x, labels)                           # the first calls of a graphed step run eagerly
+        model.module.eval()
+        with torch.no_grad():
+            for b in (B, FT_TEST_COUNT % B):      # validation: full batches and the test set's short last one
+                model.module(x[:b])
         _lib.CALL_HOOK = None
         torch.cuda.synchronize()
         out[wl] = {'gemm': sorted(gemm), 'wgrad': sorted(wgrad)}
