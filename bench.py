@@ -3,6 +3,7 @@
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
                                                                         #   (with ordered reductions: --deterministic)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full               # + every other measurement and check (below)
     python bench.py --gpus N ...        # N > 1 without a launcher: starts the N ranks itself (child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -21,12 +22,16 @@ because the metric is quoted "(N=1024,G=64) at 1/2/4/8 MI355X": its N=1 point
 is cfg3 and its N>1 points are cfg4 (local B=128 per GPU, weak scaling).
 `--workload cfg2` times the PointNet++ experiment instead (when built).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
-`roofline` for the dominant kernel (timed live with HIP events on the launch
-stream), `roofline_geometry` (FPS / kNN / Chamfer launch times against the HBM
-and the vector-op rooflines), `also.cfg2` (BASELINE config 2 as a second, short
-timed leg with the roofline of its large Chamfer kernel) and `cpu_baseline`, the
-CPU oracle (oracle/, "port") timed on the host cores on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run does only what its headline figure needs: it sets up (builds the model,
+captures the step graphs), runs the warm-up and the timed steps, writes --dump-outputs and prints the line.  With
+--full the line gains the extra objects: `roofline` for the dominant kernel (timed live with HIP events on the
+launch stream), `roofline_geometry` (FPS / kNN / Chamfer launch times against the HBM and the vector-op rooflines),
+`box_calibration` + `timed_regions`, `tvis_table` + `ddp_model`, `also.cfg2` (BASELINE config 2 as a second, short
+timed leg with the roofline of its large Chamfer kernel, then the published, DGCNN and cfg5-shape legs),
+`cpu_baseline`, the CPU oracle (oracle/, "port") timed on the host cores on a bounded sample, and with N > 1
+`replicas_in_sync`.  The --no-* switches, --probe-steps, --also-steps and --cpu-* select among those extras; they
+change nothing without --full.  Everything --full adds runs after the timed steps and the dump.  (An --eager run
+times its launches inside the timed steps, so its `roofline` is in the line either way.)
 """
 import argparse
 import json
@@ -72,6 +77,9 @@ def parse():
     p.add_argument('--batch', type=int, default=128, help='clouds per GPU')
     p.add_argument('--npoints', type=int, default=1024)
     p.add_argument('--num_group', type=int, default=64)
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps, also run every other measurement and check (rooflines, box calibration, '
+                        'T_vis table, the other workloads\' legs, CPU baseline, replica agreement); off: the headline only')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--eager', action='store_true', help='launch kernel by kernel instead of replaying hipGraphs')
     p.add_argument('--cpu-batch', type=int, default=8)
@@ -915,10 +923,11 @@ def main():
     dumped = None
     if args.dump_outputs and rank == 0:       # before anything else runs a step: the last TIMED step's outputs
         dumped = dump_outputs(args.dump_outputs, out, model, grads=not args.eager)
+    # from here to the result line everything but the ranks' slowest elapsed time runs with --full only
     # three more timed regions of 20 steps each (same bracketing; every rank runs them): their median next to the single
     # figure above, and the box calibration, so that a round-to-round delta can be told from box-to-box variance
     regions, calib = None, None
-    if not args.no_calibration:
+    if args.full and not args.no_calibration:
         regions = []
         for _ in range(3):
             torch.cuda.synchronize()
@@ -935,7 +944,7 @@ def main():
             calib = box_calibration(device)
     probe_mode = 'HIP events around every launch of the kernel inside the timed region (eager launches)'
     per_tvis = None
-    if not args.eager and rank == 0 and args.workload == 'cfg3':
+    if args.full and not args.eager and rank == 0 and args.workload == 'cfg3':
         # hipGraph replay hides individual launches from host-recorded events, so the single largest kernel (the
         # embedder's conv3: `roofline_best`) is timed with HIP events on its launch stream over `probe_steps` eager
         # forward + backward passes of the same workload, run right after the timed region (same process, same buffers,
@@ -959,13 +968,15 @@ def main():
                       'timed hipGraph region' % args.probe_steps)
     nn_ops.set_probe(None)
     table = None
-    if not args.eager and rank == 0 and args.workload == 'cfg3' and not args.no_tvis_table and isinstance(step, GraphedTrainStep):
+    if (args.full and not args.eager and rank == 0 and args.workload == 'cfg3' and not args.no_tvis_table
+            and isinstance(step, GraphedTrainStep)):
         table = tvis_table(step, batches[0])
     in_sync = None
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if world > 1 and args.full:
         # data-parallel sanity after the timed steps: every replica must hold bit-identical parameters
         # (same broadcast start, same averaged gradients, same update) -- max and min over ranks of a
         # checksum pair agree exactly or the collective path is broken
@@ -1012,7 +1023,7 @@ def main():
         line = {
             'metric': 'pretrain point-clouds/sec (N=%d,G=%d)' % (args.npoints, args.num_group), 'value': clouds_per_s, 'unit': 'clouds/s',
             'n_gpus': world, 'rccl_ranks': (dist.get_world_size() if world > 1 and backend == 'nccl' else (1 if world == 1 else 0)),
-            'steps': args.steps, 'warmup': args.warmup,
+            'steps': args.steps, 'warmup': args.warmup, 'full': args.full,
             'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
             'vs_baseline': None,
             'dtype': 'f32 (3xbf16 exact-split operands, fp32 accumulate)' if bf16x3 else 'f32', 'data': 'synthetic',
@@ -1072,9 +1083,9 @@ def main():
             line['tvis_table'] = {'unit': 'ms per replay (forward + loss + backward graph(s), no AdamW)',
                                   'ms': {str(t): round(v, 4) for t, v in table.items()}}
             line['ddp_model'] = ddp_model(table, args.num_group, elapsed / args.steps * 1e3)
-        if world > 1:
+        if world > 1 and args.full:
             line['replicas_in_sync'] = in_sync          # parameters bit-identical on all ranks after the timed steps
-        if args.workload == 'cfg3' and not args.no_also:
+        if args.full and args.workload == 'cfg3' and not args.no_also:
             line['roofline_geometry'] = geometry_rooflines(args, clouds)
             if world == 1:
                 del step
@@ -1082,7 +1093,7 @@ def main():
                 line['also']['published_variant'] = published_leg(args, device, rank)
                 line['also']['dgcnn'] = dgcnn_leg(args, device, rank)
                 line['also']['cfg5_shape'] = cfg5_leg(args, device, rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(config, args)
             line['cpu_baseline']['whole_box'] = cpu_baseline_box(args, line['cpu_baseline'])
         print(json.dumps(line), flush=True)

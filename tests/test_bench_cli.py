@@ -70,6 +70,47 @@ def test_steps_below_one_is_refused():
     assert '{"metric"' not in r.stdout
 
 
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run measures the headline only; --full asks for every other measurement and check."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1'])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--full'])
+    assert bench.parse().full is True
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_full_adds_the_extras():
+    """Without --full the line holds the headline figure and none of the extra measurements; with --full (here without
+    the other workloads' legs and the CPU baseline) the rooflines, the T_vis table and the box calibration come back."""
+    import json
+    import proc_util
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'PDAE_BENCH_BACKEND')}
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '16']
+    lines = {}
+    for name, extra in (('plain', []), ('full', ['--full', '--no-also', '--no-cpu-baseline', '--probe-steps', '1'])):
+        r = proc_util.run(base + extra, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-4000:]
+        got = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(got) == 1, r.stdout[-2000:]
+        lines[name] = json.loads(got[0])
+    for d in lines.values():
+        assert d['metric'] == 'pretrain point-clouds/sec (N=1024,G=64)' and d['unit'] == 'clouds/s'
+        assert d['higher_is_better'] is True and d['value'] > 0 and d['ms_per_step'] > 0 and d['dtype']
+        assert d['steps'] == 2 and d['warmup'] == 1
+    plain, full = lines['plain'], lines['full']
+    assert plain['full'] is False and full['full'] is True
+    assert plain['roofline'] is None and plain['box_calibration'] is None and plain['timed_regions'] is None
+    for key in ('roofline_geometry', 'also', 'cpu_baseline', 'tvis_table', 'ddp_model', 'whole_step'):
+        assert key not in plain, key
+    assert full['roofline'] is not None and full['timed_regions'] is not None and 'mfma_bf16' in full['box_calibration']
+    assert full['tvis_table'] and full['ddp_model'] and full['whole_step']
+    assert 'also' not in full and 'cpu_baseline' not in full
+
+
 def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
     """--dump-outputs DIR: the step's two losses and the flat parameter / gradient buffers as float32 .npy files, at most
     64 MB in all; buffers too large for that are written as the same seeded sample of elements in every run."""

@@ -158,7 +158,7 @@ def test_bench_two_ranks_code_path(launcher):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     tail = [os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--batch', '8',
-            '--probe-steps', '2']
+            '--probe-steps', '2', '--full']
     if launcher == 'torchrun':
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                '--master-addr', '127.0.0.1', '--master-port', str(_free_port())] + tail

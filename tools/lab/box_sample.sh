@@ -2,7 +2,7 @@
 # One line per box: the default step time next to the box calibration (bench.py box_calibration) -- run it several times,
 # every gpurun call lands on another box:   gpurun -- bash tools/lab/box_sample.sh
 cd "$GRAFT_REPO_ROOT"
-python bench.py --no-cpu-baseline --no-also --no-tvis-table --probe-steps 0 2>/dev/null | grep '"metric"' | tail -1 | python -c '
+python bench.py --full --no-cpu-baseline --no-also --no-tvis-table --probe-steps 0 2>/dev/null | grep '"metric"' | tail -1 | python -c '
 import sys, json
 d = json.loads(sys.stdin.read())
 c, r = d["box_calibration"], d["timed_regions"]

@@ -9,11 +9,13 @@ python -c "import sys; sys.exit(0 if float('$ms') < float('$LIMIT') else 1)" || 
 bash tools/prof_round.sh > gpurun_out/round.log 2>&1
 bash tools/prof_cfg2.sh > /dev/null 2>&1
 bash tools/prof_dgcnn.sh > /dev/null 2>&1
-python bench.py > gpurun_out/bench_final.json 2> gpurun_out/bench_final.err
+line=$(python bench.py --full 2> /dev/null | grep '"metric"' | tail -1)
+echo "$line"
 echo "done: $(head -2 gpurun_out/round/kernel_summary.txt | tail -1)"
-python - <<'PY'
+python - "$line" <<'PY'
 import json
-d = json.loads(open('gpurun_out/bench_final.json').read().strip().splitlines()[-1])
+import sys
+d = json.loads(sys.argv[1])
 a = d['also']
 print(d['ms_per_step'], d['value'], 'cfg2', a['cfg2']['ms_per_step'], 'pub', a['published_variant']['ms_per_step'], 'dgcnn', a['dgcnn']['ms_per_step'], 'cfg5', a['cfg5_shape']['ms_per_step'])
 PY

@@ -1,14 +1,16 @@
 #!/bin/bash
-# What the driver runs at round end, in one call on the GPU box:  gpurun --timeout 1500 -- bash tools/preflight.sh
-#   smoke() on cuda:0, the -m gpu suite, the default bench line (-> gpurun_out/preflight_*.{txt,json})
-cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+# The end-of-round check in one GPU session:   bash tools/preflight.sh OUTDIR
+#   smoke() on cuda:0, the -m gpu suite, the full bench line (bench.py --full) -> OUTDIR/preflight_*.{txt,json,err}
+OUT=${1:?usage: bash tools/preflight.sh OUTDIR}
+mkdir -p "$OUT" && OUT=$(cd "$OUT" && pwd) || exit 1
+cd "$(dirname "$0")/.."
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 1200 python -m pytest tests -m gpu -x -q > gpurun_out/preflight_tests.txt 2>&1; echo "pytest rc=$? $(tail -1 gpurun_out/preflight_tests.txt)"
-python bench.py > gpurun_out/preflight_bench.json 2> gpurun_out/preflight_bench.err; echo "bench rc=$?"
-python - <<'PY'
+timeout 1200 python -m pytest tests -m gpu -x -q > "$OUT/preflight_tests.txt" 2>&1; echo "pytest rc=$? $(tail -1 "$OUT/preflight_tests.txt")"
+python bench.py --full > "$OUT/preflight_bench.json" 2> "$OUT/preflight_bench.err"; echo "bench rc=$?"
+python - "$OUT/preflight_bench.json" <<'PY'
 import json
-d = json.loads(open('gpurun_out/preflight_bench.json').read().strip().splitlines()[-1])
+import sys
+d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 a = d['also']
 print('ms/step %.3f  clouds/s %.0f  roofline %.3f (%.1f TFLOP/s-eq, %.2f ms of families)  best %.3f  whole-step %.1f TFLOP/s  cfg2 %.2f ms  published %.2f ms  '
       'dgcnn %.2f ms  cfg5-shape %.2f ms  cpu %.1f clouds/s' % (
