@@ -6,16 +6,19 @@
 //   pdae_bn_relu_dropout / _grad  Linear -> BatchNorm1d -> ReLU -> Dropout(p) of cls_head_finetune (:616-626) after its
 //                                 Linear: batch statistics, running estimates, the affine, ReLU and the dropout mask in
 //                                 ONE launch (a thread owns a column and walks the B rows), backward likewise
-//   pdae_softmax_xent / _grad     nn.CrossEntropyLoss() (mean) + the argmax hit count (get_loss_acc, :634-638)
 //   pdae_bn_lrelu_dropout / _grad the same for DGCNN's head (models/PointCAE_DGCNN.py:572-663): BatchNorm1d ->
-//                                 LeakyReLU(slope) -> Dropout(p), a sibling of bn_relu_dropout (whose kernels stay as
-//                                 they are); at slope 0 it gives bn_relu_dropout's bits
+//                                 LeakyReLU(slope) -> Dropout(p); at slope 0 it gives bn_relu_dropout's bits.  Both
+//                                 entries launch bn_act_dropout_kernel / _grad_kernel, templated on the activation
+//   pdae_softmax_xent / _grad     nn.CrossEntropyLoss() (mean) + the argmax hit count (get_loss_acc, :634-638)
 //   pdae_softmax_xent_smooth / _grad  DGCNN's smoothloss (get_loss_acc, :592-600): cross-entropy against the target
-//                                 t = onehot (1 - eps) + (1 - onehot) eps / (K - 1), + the same hit count
+//                                 t = onehot (1 - eps) + (1 - onehot) eps / (K - 1), + the same hit count.  Both entries
+//                                 launch softmax_xent_kernel / _grad_kernel, templated on the target
 //   pdae_grad_norm_clip           torch.nn.utils.clip_grad_norm_ (runner_finetune.py:201-202) on the flat gradient
 //                                 buffer: per-block fp64 partials, then one block adds them in block order; the
 //                                 clip coefficient stays on the device (AdamW reads it: pdae_adamw_step_gscale)
 // Every reduction runs in a fixed order (no float atomics): results do not depend on scheduling.
+#include <string>
+
 #include "common.h"
 
 namespace pdae {
@@ -86,14 +89,18 @@ __global__ __launch_bounds__(256) void cls_max_concat_grad_kernel(long long n, i
 
 // thread per column n of y (B, N).  Training: fp64 mean and biased variance over the B rows (two passes), the running
 // estimates with the unbiased variance (nn.BatchNorm1d), mean / invstd saved for the backward; eval: the running
-// estimates.  out = relu((y - mean) gamma invstd + beta) * (u >= p ? 1 / (1 - p) : 0); u null: no dropout
-__global__ __launch_bounds__(256) void bn_relu_dropout_kernel(int B, int N, const float* __restrict__ y,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              float eps, float momentum, float* __restrict__ rmean,
-                                                              float* __restrict__ rvar, long long* __restrict__ counter,
-                                                              int training, float p, const float* __restrict__ u,
-                                                              float* __restrict__ out, float* __restrict__ mean,
-                                                              float* __restrict__ invstd) {
+// estimates.  out = act((y - mean) gamma invstd + beta) * (u >= p ? 1 / (1 - p) : 0); u null: no dropout.
+// act = relu, or (LEAKY) LeakyReLU: max(v, 0) + slope min(v, 0) -- one of the two terms is 0, so it is torch's
+// `v > 0 ? v : v * slope` with a +0 (never -0) for v <= 0 at slope 0, as fmaxf(v, 0) gives.  The two activations keep
+// separate expressions: LEAKY at slope 0 gives the ReLU instantiation's bits through that signed-zero argument
+template <bool LEAKY>
+__global__ __launch_bounds__(256) void bn_act_dropout_kernel(int B, int N, const float* __restrict__ y,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             float eps, float momentum, float* __restrict__ rmean,
+                                                             float* __restrict__ rvar, long long* __restrict__ counter,
+                                                             int training, float p, float slope,
+                                                             const float* __restrict__ u, float* __restrict__ out,
+                                                             float* __restrict__ mean, float* __restrict__ invstd) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (training && n == 0 && counter) *counter += 1;
   if (n >= N) return;
@@ -122,20 +129,32 @@ __global__ __launch_bounds__(256) void bn_relu_dropout_kernel(int B, int N, cons
   const float keep_scale = 1.0f / (1.0f - p);
   for (int r = 0; r < B; ++r) {
     const size_t k = (size_t)r * N + n;
-    float v = fmaxf((y[k] - m) * sc + be, 0.f);       // centred first: no cancellation when the variance is small
+    const float z = (y[k] - m) * sc + be;             // centred first: no cancellation when the variance is small
+    float v;
+    if constexpr (LEAKY) v = fmaxf(z, 0.f) + slope * fminf(z, 0.f);
+    else v = fmaxf(z, 0.f);
     if (u) v = u[k] >= p ? v * keep_scale : 0.f;
     out[k] = v;
   }
 }
 
-// backward of the training-mode forward, thread per column: g = dout * dropout mask * relu'(.); dbeta = sum g,
+// dout times the activation's derivative at z = the forward's pre-activation (same arithmetic): 1 for z > 0, else 0
+// (ReLU) or slope (LEAKY; `+ 0.f` turns slope * dout = -0 into +0, so that slope 0 gives ReLU's bits)
+template <bool LEAKY>
+__device__ __forceinline__ float act_grad(float z, const float* __restrict__ dout, float slope) {
+  if constexpr (LEAKY) return z > 0.f ? *dout : slope * *dout + 0.f;
+  else return z > 0.f ? *dout : 0.f;
+}
+
+// backward of the training-mode forward, thread per column: g = dout * dropout mask * act'(.); dbeta = sum g,
 // dgamma = sum g xhat (fp64, rows in order); dy = gamma invstd (g - dbeta / B - xhat dgamma / B)
-__global__ __launch_bounds__(256) void bn_relu_dropout_grad_kernel(int B, int N, const float* __restrict__ y,
-                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                   const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                   float p, const float* __restrict__ u,
-                                                                   const float* __restrict__ dout, float* __restrict__ dy,
-                                                                   float* __restrict__ dgamma, float* __restrict__ dbeta) {
+template <bool LEAKY>
+__global__ __launch_bounds__(256) void bn_act_dropout_grad_kernel(int B, int N, const float* __restrict__ y,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                  float slope, float p, const float* __restrict__ u,
+                                                                  const float* __restrict__ dout, float* __restrict__ dy,
+                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const float m = mean[n], is = invstd[n], ga = gamma[n];
@@ -145,7 +164,7 @@ __global__ __launch_bounds__(256) void bn_relu_dropout_grad_kernel(int B, int N,
   for (int r = 0; r < B; ++r) {
     const size_t k = (size_t)r * N + n;
     const float x = y[k];
-    float g = (x - m) * sc + be > 0.f ? dout[k] : 0.f;       // the forward's ReLU test, same arithmetic
+    float g = act_grad<LEAKY>((x - m) * sc + be, dout + k, slope);
     if (u) g = u[k] >= p ? g * keep_scale : 0.f;
     sg += (double)g;
     sgx += (double)g * (double)((x - m) * is);
@@ -156,86 +175,7 @@ __global__ __launch_bounds__(256) void bn_relu_dropout_grad_kernel(int B, int N,
   for (int r = 0; r < B; ++r) {
     const size_t k = (size_t)r * N + n;
     const float x = y[k];
-    float g = (x - m) * sc + be > 0.f ? dout[k] : 0.f;
-    if (u) g = u[k] >= p ? g * keep_scale : 0.f;
-    dy[k] = sc * (g - c1 - (x - m) * is * c2);
-  }
-}
-
-// bn_relu_dropout_kernel with LeakyReLU: act(v) = max(v, 0) + slope min(v, 0) -- one of the two terms is 0, so it is
-// torch's `v > 0 ? v : v * slope` with a +0 (never -0) for v <= 0 at slope 0, as fmaxf(v, 0) gives
-__global__ __launch_bounds__(256) void bn_lrelu_dropout_kernel(int B, int N, const float* __restrict__ y,
-                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                               float eps, float momentum, float* __restrict__ rmean,
-                                                               float* __restrict__ rvar, long long* __restrict__ counter,
-                                                               int training, float slope, float p,
-                                                               const float* __restrict__ u, float* __restrict__ out,
-                                                               float* __restrict__ mean, float* __restrict__ invstd) {
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (training && n == 0 && counter) *counter += 1;
-  if (n >= N) return;
-  float m, is;
-  if (training) {
-    double s1 = 0.0;
-    for (int r = 0; r < B; ++r) s1 += (double)y[(size_t)r * N + n];
-    const double mu = s1 / B;
-    double s2 = 0.0;
-    for (int r = 0; r < B; ++r) {
-      const double d = (double)y[(size_t)r * N + n] - mu;
-      s2 += d * d;
-    }
-    const double var = s2 / B;
-    m = (float)mu;
-    is = 1.0f / sqrtf((float)var + eps);
-    if (rmean) rmean[n] = (1.0f - momentum) * rmean[n] + momentum * m;
-    if (rvar) rvar[n] = (1.0f - momentum) * rvar[n] + momentum * (float)(s2 / (B - 1));
-    mean[n] = m;
-    invstd[n] = is;
-  } else {
-    m = rmean[n];
-    is = 1.0f / sqrtf(rvar[n] + eps);
-  }
-  const float sc = gamma[n] * is, be = beta[n];
-  const float keep_scale = 1.0f / (1.0f - p);
-  for (int r = 0; r < B; ++r) {
-    const size_t k = (size_t)r * N + n;
-    const float z = (y[k] - m) * sc + be;
-    float v = fmaxf(z, 0.f) + slope * fminf(z, 0.f);
-    if (u) v = u[k] >= p ? v * keep_scale : 0.f;
-    out[k] = v;
-  }
-}
-
-// backward of bn_lrelu_dropout_kernel (training mode), bn_relu_dropout_grad_kernel's arithmetic with the LeakyReLU
-// derivative: g = dout * dropout mask * (z > 0 ? 1 : slope), z recomputed as the forward computes it.  `+ 0.f` turns
-// slope * dout = -0 into +0, so that slope 0 gives bn_relu_dropout_grad's bits
-__global__ __launch_bounds__(256) void bn_lrelu_dropout_grad_kernel(int B, int N, const float* __restrict__ y,
-                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                    const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                    float slope, float p, const float* __restrict__ u,
-                                                                    const float* __restrict__ dout, float* __restrict__ dy,
-                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  const float m = mean[n], is = invstd[n], ga = gamma[n];
-  const float sc = ga * is, be = beta[n];
-  const float keep_scale = 1.0f / (1.0f - p);
-  double sg = 0.0, sgx = 0.0;
-  for (int r = 0; r < B; ++r) {
-    const size_t k = (size_t)r * N + n;
-    const float x = y[k];
-    float g = (x - m) * sc + be > 0.f ? dout[k] : slope * dout[k] + 0.f;
-    if (u) g = u[k] >= p ? g * keep_scale : 0.f;
-    sg += (double)g;
-    sgx += (double)g * (double)((x - m) * is);
-  }
-  dbeta[n] = (float)sg;
-  dgamma[n] = (float)sgx;
-  const float c1 = (float)(sg / B), c2 = (float)(sgx / B);
-  for (int r = 0; r < B; ++r) {
-    const size_t k = (size_t)r * N + n;
-    const float x = y[k];
-    float g = (x - m) * sc + be > 0.f ? dout[k] : slope * dout[k] + 0.f;
+    float g = act_grad<LEAKY>((x - m) * sc + be, dout + k, slope);
     if (u) g = u[k] >= p ? g * keep_scale : 0.f;
     dy[k] = sc * (g - c1 - (x - m) * is * c2);
   }
@@ -250,10 +190,15 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// one wave per row (lane = class, K <= 64): lse = max + log sum exp(x - max); loss_r = lse - x[label]; hit_r = argmax == label
-// (ties: the lowest class).  Row results in shared memory, added in row order by thread 0.
+// one wave per row (lane = class, K <= 64): lse = max + log sum exp(x - max); loss_r = lse - (the target term);
+// hit_r = argmax == label (ties: the lowest class).  Row results in shared memory, added in row order by thread 0.
+// The target term is x[label] (nn.CrossEntropyLoss), or (SMOOTH) sum_k t_k x_k against the smoothed target
+// t_k = k == label ? on : off (the lane products added by the wave's butterfly); at eps = 0 that sum is x[label]
+// plus zeros: the plain instantiation's bits
 constexpr int XENT_MAX_B = 4096;
-__global__ __launch_bounds__(256) void softmax_xent_kernel(int B, int K, const float* __restrict__ logits,
+template <bool SMOOTH>
+__global__ __launch_bounds__(256) void softmax_xent_kernel(int B, int K, float on, float off,
+                                                           const float* __restrict__ logits,
                                                            const int64_t* __restrict__ labels, float* __restrict__ loss,
                                                            float* __restrict__ correct) {
   __shared__ float rl[XENT_MAX_B];
@@ -265,56 +210,10 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(int B, int K, const f
     const float s = wave_sum(lane < K ? expf(x - mx) : 0.f);
     const int64_t lab = labels[r];
     const bool ok = lab >= 0 && lab < K;
-    const float xl = __shfl(x, ok ? (int)lab : 0);
+    float tx;
+    if constexpr (SMOOTH) tx = wave_sum(lane < K ? (lane == lab ? on : off) * x : 0.f);
+    else tx = __shfl(x, ok ? (int)lab : 0);
     // the first lane holding the maximum
-    const unsigned long long at = __ballot(lane < K && x == mx);
-    const int am = __ffsll((long long)at) - 1;
-    if (lane == 0) {
-      rl[r] = ok ? (mx + logf(s)) - xl : NAN;
-      rh[r] = ok && am == lab;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f, h = 0.f;
-    for (int r = 0; r < B; ++r) t += rl[r], h += rh[r];
-    *loss = t / B;
-    *correct = h;
-  }
-}
-
-// dlogits[r][k] = (softmax(x_r)[k] - (k == label_r)) * dloss / B, one wave per row
-__global__ __launch_bounds__(256) void softmax_xent_grad_kernel(int B, int K, const float* __restrict__ logits,
-                                                                const int64_t* __restrict__ labels,
-                                                                const float* __restrict__ dloss, float* __restrict__ dlogits) {
-  const int lane = lane_id();
-  const int r = blockIdx.x * 4 + threadIdx.x / kWave;
-  if (r >= B) return;
-  const float x = lane < K ? logits[(size_t)r * K + lane] : -INFINITY;
-  const float mx = wave_max(x);
-  const float e = lane < K ? expf(x - mx) : 0.f;
-  const float s = wave_sum(e);
-  const float scale = *dloss / (float)B;
-  if (lane < K) dlogits[(size_t)r * K + lane] = (e / s - (labels[r] == lane ? 1.f : 0.f)) * scale;
-}
-
-// softmax_xent_kernel against the smoothed target t_k = k == label ? 1 - eps : eps / (K - 1):
-// loss_r = lse - sum_k t_k x_k (the lane products added by the wave's butterfly); the hit count as softmax_xent.
-// At eps = 0 the sum is x[label] plus zeros: softmax_xent's bits
-__global__ __launch_bounds__(256) void softmax_xent_smooth_kernel(int B, int K, float on, float off,
-                                                                  const float* __restrict__ logits,
-                                                                  const int64_t* __restrict__ labels,
-                                                                  float* __restrict__ loss, float* __restrict__ correct) {
-  __shared__ float rl[XENT_MAX_B];
-  __shared__ unsigned char rh[XENT_MAX_B];
-  const int lane = lane_id(), w = threadIdx.x / kWave;
-  for (int r = w; r < B; r += 4) {
-    const float x = lane < K ? logits[(size_t)r * K + lane] : -INFINITY;
-    const float mx = wave_max(x);
-    const float s = wave_sum(lane < K ? expf(x - mx) : 0.f);
-    const int64_t lab = labels[r];
-    const bool ok = lab >= 0 && lab < K;
-    const float tx = wave_sum(lane < K ? (lane == lab ? on : off) * x : 0.f);
     const unsigned long long at = __ballot(lane < K && x == mx);
     const int am = __ffsll((long long)at) - 1;
     if (lane == 0) {
@@ -331,12 +230,12 @@ __global__ __launch_bounds__(256) void softmax_xent_smooth_kernel(int B, int K, 
   }
 }
 
-// dlogits[r][k] = (softmax(x_r)[k] - t_k) * dloss / B, one wave per row
-__global__ __launch_bounds__(256) void softmax_xent_smooth_grad_kernel(int B, int K, float on, float off,
-                                                                       const float* __restrict__ logits,
-                                                                       const int64_t* __restrict__ labels,
-                                                                       const float* __restrict__ dloss,
-                                                                       float* __restrict__ dlogits) {
+// dlogits[r][k] = (softmax(x_r)[k] - t_k) * dloss / B, one wave per row; t = the one-hot label, or (SMOOTH) on / off
+template <bool SMOOTH>
+__global__ __launch_bounds__(256) void softmax_xent_grad_kernel(int B, int K, float on, float off,
+                                                                const float* __restrict__ logits,
+                                                                const int64_t* __restrict__ labels,
+                                                                const float* __restrict__ dloss, float* __restrict__ dlogits) {
   const int lane = lane_id();
   const int r = blockIdx.x * 4 + threadIdx.x / kWave;
   if (r >= B) return;
@@ -345,7 +244,8 @@ __global__ __launch_bounds__(256) void softmax_xent_smooth_grad_kernel(int B, in
   const float e = lane < K ? expf(x - mx) : 0.f;
   const float s = wave_sum(e);
   const float scale = *dloss / (float)B;
-  if (lane < K) dlogits[(size_t)r * K + lane] = (e / s - (labels[r] == lane ? on : off)) * scale;
+  if (lane < K)
+    dlogits[(size_t)r * K + lane] = (e / s - (labels[r] == lane ? (SMOOTH ? on : 1.f) : (SMOOTH ? off : 0.f))) * scale;
 }
 
 // per-block partial sums of squares of g (float4 grid-stride; each thread adds its squares in fp32 groups of 4, the
@@ -442,124 +342,136 @@ extern "C" int pdae_cls_max_concat_grad(int B, int T, int C, const float* dout, 
   return check_launch("cls_max_concat_grad");
 }
 
+// "<what>: <msg>" through bad_arg or unsupported: the entry's error text and status
+static int fail(int (*status)(const char*), const char* what, const char* msg) {
+  return status((std::string(what) + ": " + msg).c_str());
+}
+
+// the checks and the launch behind pdae_bn_relu_dropout and (LEAKY) pdae_bn_lrelu_dropout
+template <bool LEAKY>
+static int bn_act_dropout(const char* what, int B, int N, const float* y, const float* gamma, const float* beta, float eps,
+                          float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
+                          int training, float slope, float p, const float* u, float* out, float* mean, float* invstd,
+                          pdae_stream_t stream) {
+  if (B < 1 || N < 1) return fail(bad_arg, what, "B >= 1 and N >= 1 required");
+  if (!y || !gamma || !beta || !out) return fail(bad_arg, what, "null pointer");
+  if (LEAKY && !(slope >= 0.f && slope < 1.f)) return fail(bad_arg, what, "0 <= negative_slope < 1 required");
+  if (training) {
+    if (B < 2) return fail(bad_arg, what, "training-mode batch statistics need B >= 2");
+    if (!mean || !invstd) return fail(bad_arg, what, "training mode writes mean and invstd");
+    if (!(p >= 0.f && p < 1.f)) return fail(bad_arg, what, "0 <= p < 1 required");
+  } else {
+    if (!running_mean || !running_var) return fail(bad_arg, what, "eval mode reads the running estimates");
+    u = nullptr;
+  }
+  hipLaunchKernelGGL(bn_act_dropout_kernel<LEAKY>, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y, gamma,
+                     beta, eps, momentum, running_mean, running_var, num_batches_tracked, training, p, slope, u, out, mean,
+                     invstd);
+  return check_launch(what);
+}
+
+template <bool LEAKY>
+static int bn_act_dropout_grad(const char* what, int B, int N, const float* y, const float* gamma, const float* beta,
+                               const float* mean, const float* invstd, float slope, float p, const float* u,
+                               const float* dout, float* dy, float* dgamma, float* dbeta, pdae_stream_t stream) {
+  if (B < 2 || N < 1) return fail(bad_arg, what, "B >= 2 and N >= 1 required");
+  if (LEAKY && !(slope >= 0.f && slope < 1.f)) return fail(bad_arg, what, "0 <= negative_slope < 1 required");
+  if (!(p >= 0.f && p < 1.f)) return fail(bad_arg, what, "0 <= p < 1 required");
+  if (!y || !gamma || !beta || !mean || !invstd || !dout || !dy || !dgamma || !dbeta) return fail(bad_arg, what, "null pointer");
+  hipLaunchKernelGGL(bn_act_dropout_grad_kernel<LEAKY>, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y,
+                     gamma, beta, mean, invstd, slope, p, u, dout, dy, dgamma, dbeta);
+  return check_launch(what);
+}
+
 extern "C" int pdae_bn_relu_dropout(int B, int N, const float* y, const float* gamma, const float* beta, float eps,
                                     float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
                                     int training, float p, const float* u, float* out, float* mean, float* invstd,
                                     pdae_stream_t stream) {
-  if (B < 1 || N < 1) return bad_arg("bn_relu_dropout: B >= 1 and N >= 1 required");
-  if (!y || !gamma || !beta || !out) return bad_arg("bn_relu_dropout: null pointer");
-  if (training) {
-    if (B < 2) return bad_arg("bn_relu_dropout: training-mode batch statistics need B >= 2");
-    if (!mean || !invstd) return bad_arg("bn_relu_dropout: training mode writes mean and invstd");
-    if (!(p >= 0.f && p < 1.f)) return bad_arg("bn_relu_dropout: 0 <= p < 1 required");
-  } else {
-    if (!running_mean || !running_var) return bad_arg("bn_relu_dropout: eval mode reads the running estimates");
-    u = nullptr;
-  }
-  hipLaunchKernelGGL(bn_relu_dropout_kernel, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y, gamma, beta, eps,
-                     momentum, running_mean, running_var, num_batches_tracked, training, p, u, out, mean, invstd);
-  return check_launch("bn_relu_dropout");
+  return bn_act_dropout<false>("bn_relu_dropout", B, N, y, gamma, beta, eps, momentum, running_mean, running_var,
+                               num_batches_tracked, training, 0.f, p, u, out, mean, invstd, stream);
 }
 
 extern "C" int pdae_bn_relu_dropout_grad(int B, int N, const float* y, const float* gamma, const float* beta,
                                          const float* mean, const float* invstd, float p, const float* u,
                                          const float* dout, float* dy, float* dgamma, float* dbeta, pdae_stream_t stream) {
-  if (B < 2 || N < 1) return bad_arg("bn_relu_dropout_grad: B >= 2 and N >= 1 required");
-  if (!(p >= 0.f && p < 1.f)) return bad_arg("bn_relu_dropout_grad: 0 <= p < 1 required");
-  if (!y || !gamma || !beta || !mean || !invstd || !dout || !dy || !dgamma || !dbeta)
-    return bad_arg("bn_relu_dropout_grad: null pointer");
-  hipLaunchKernelGGL(bn_relu_dropout_grad_kernel, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y, gamma, beta,
-                     mean, invstd, p, u, dout, dy, dgamma, dbeta);
-  return check_launch("bn_relu_dropout_grad");
+  return bn_act_dropout_grad<false>("bn_relu_dropout_grad", B, N, y, gamma, beta, mean, invstd, 0.f, p, u, dout, dy,
+                                    dgamma, dbeta, stream);
 }
 
 extern "C" int pdae_bn_lrelu_dropout(int B, int N, const float* y, const float* gamma, const float* beta, float eps,
                                      float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
                                      int training, float negative_slope, float p, const float* u, float* out, float* mean,
                                      float* invstd, pdae_stream_t stream) {
-  if (B < 1 || N < 1) return bad_arg("bn_lrelu_dropout: B >= 1 and N >= 1 required");
-  if (!y || !gamma || !beta || !out) return bad_arg("bn_lrelu_dropout: null pointer");
-  if (!(negative_slope >= 0.f && negative_slope < 1.f)) return bad_arg("bn_lrelu_dropout: 0 <= negative_slope < 1 required");
-  if (training) {
-    if (B < 2) return bad_arg("bn_lrelu_dropout: training-mode batch statistics need B >= 2");
-    if (!mean || !invstd) return bad_arg("bn_lrelu_dropout: training mode writes mean and invstd");
-    if (!(p >= 0.f && p < 1.f)) return bad_arg("bn_lrelu_dropout: 0 <= p < 1 required");
-  } else {
-    if (!running_mean || !running_var) return bad_arg("bn_lrelu_dropout: eval mode reads the running estimates");
-    u = nullptr;
-  }
-  hipLaunchKernelGGL(bn_lrelu_dropout_kernel, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y, gamma, beta,
-                     eps, momentum, running_mean, running_var, num_batches_tracked, training, negative_slope, p, u, out, mean,
-                     invstd);
-  return check_launch("bn_lrelu_dropout");
+  return bn_act_dropout<true>("bn_lrelu_dropout", B, N, y, gamma, beta, eps, momentum, running_mean, running_var,
+                              num_batches_tracked, training, negative_slope, p, u, out, mean, invstd, stream);
 }
 
 extern "C" int pdae_bn_lrelu_dropout_grad(int B, int N, const float* y, const float* gamma, const float* beta,
                                           const float* mean, const float* invstd, float negative_slope, float p,
                                           const float* u, const float* dout, float* dy, float* dgamma, float* dbeta,
                                           pdae_stream_t stream) {
-  if (B < 2 || N < 1) return bad_arg("bn_lrelu_dropout_grad: B >= 2 and N >= 1 required");
-  if (!(negative_slope >= 0.f && negative_slope < 1.f))
-    return bad_arg("bn_lrelu_dropout_grad: 0 <= negative_slope < 1 required");
-  if (!(p >= 0.f && p < 1.f)) return bad_arg("bn_lrelu_dropout_grad: 0 <= p < 1 required");
-  if (!y || !gamma || !beta || !mean || !invstd || !dout || !dy || !dgamma || !dbeta)
-    return bad_arg("bn_lrelu_dropout_grad: null pointer");
-  hipLaunchKernelGGL(bn_lrelu_dropout_grad_kernel, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y, gamma,
-                     beta, mean, invstd, negative_slope, p, u, dout, dy, dgamma, dbeta);
-  return check_launch("bn_lrelu_dropout_grad");
+  return bn_act_dropout_grad<true>("bn_lrelu_dropout_grad", B, N, y, gamma, beta, mean, invstd, negative_slope, p, u,
+                                   dout, dy, dgamma, dbeta, stream);
+}
+
+// the checks of the cross-entropy entries (have_ptrs: no null pointer among them); SMOOTH: one text for the shape and
+// eps checks, and the target's two values as the reference forms them in fp32: one_hot * (1 - eps) + (1 - one_hot) *
+// eps / (K - 1).  The plain loss takes K = 1, the smoothed one needs K >= 2
+template <bool SMOOTH>
+static int xent_args(const char* what, int B, int K, float eps, bool have_ptrs, float* on, float* off) {
+  if (SMOOTH) {
+    const char* req = "B in [1, 4096], K in [2, 64] and eps in [0, 1] required";
+    if (B < 1 || K < 2) return fail(bad_arg, what, req);
+    if (K > kWave || B > XENT_MAX_B) return fail(unsupported, what, req);
+    if (!(eps >= 0.f && eps <= 1.f)) return fail(bad_arg, what, req);
+    *on = 1.0f - eps;
+    *off = eps / (float)(K - 1);
+  } else {
+    if (B < 1 || K < 1) return fail(bad_arg, what, "B >= 1 and K >= 1 required");
+    if (K > kWave || B > XENT_MAX_B) return fail(unsupported, what, "K <= 64 classes and B <= 4096 rows");
+  }
+  if (!have_ptrs) return fail(bad_arg, what, "null pointer");
+  return PDAE_OK;
+}
+
+template <bool SMOOTH>
+static int softmax_xent(const char* what, int B, int K, float eps, const float* logits, const int64_t* labels, float* loss,
+                        float* correct, pdae_stream_t stream) {
+  float on = 0.f, off = 0.f;
+  if (const int st = xent_args<SMOOTH>(what, B, K, eps, logits && labels && loss && correct, &on, &off)) return st;
+  hipLaunchKernelGGL(softmax_xent_kernel<SMOOTH>, dim3(1), dim3(256), 0, as_stream(stream), B, K, on, off, logits, labels,
+                     loss, correct);
+  return check_launch(what);
+}
+
+template <bool SMOOTH>
+static int softmax_xent_grad(const char* what, int B, int K, float eps, const float* logits, const int64_t* labels,
+                             const float* dloss, float* dlogits, pdae_stream_t stream) {
+  float on = 0.f, off = 0.f;
+  if (const int st = xent_args<SMOOTH>(what, B, K, eps, logits && labels && dloss && dlogits, &on, &off)) return st;
+  hipLaunchKernelGGL(softmax_xent_grad_kernel<SMOOTH>, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), B, K, on, off,
+                     logits, labels, dloss, dlogits);
+  return check_launch(what);
 }
 
 extern "C" int pdae_softmax_xent(int B, int K, const float* logits, const int64_t* labels, float* loss, float* correct,
                                  pdae_stream_t stream) {
-  if (B < 1 || K < 1) return bad_arg("softmax_xent: B >= 1 and K >= 1 required");
-  if (K > kWave || B > XENT_MAX_B) return unsupported("softmax_xent: K <= 64 classes and B <= 4096 rows");
-  if (!logits || !labels || !loss || !correct) return bad_arg("softmax_xent: null pointer");
-  hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(256), 0, as_stream(stream), B, K, logits, labels, loss, correct);
-  return check_launch("softmax_xent");
+  return softmax_xent<false>("softmax_xent", B, K, 0.f, logits, labels, loss, correct, stream);
 }
 
 extern "C" int pdae_softmax_xent_grad(int B, int K, const float* logits, const int64_t* labels, const float* dloss,
                                       float* dlogits, pdae_stream_t stream) {
-  if (B < 1 || K < 1) return bad_arg("softmax_xent_grad: B >= 1 and K >= 1 required");
-  if (K > kWave || B > XENT_MAX_B) return unsupported("softmax_xent_grad: K <= 64 classes and B <= 4096 rows");
-  if (!logits || !labels || !dloss || !dlogits) return bad_arg("softmax_xent_grad: null pointer");
-  hipLaunchKernelGGL(softmax_xent_grad_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), B, K, logits, labels, dloss,
-                     dlogits);
-  return check_launch("softmax_xent_grad");
-}
-
-// the target's two values as the reference forms them in fp32: one_hot * (1 - eps) + (1 - one_hot) * eps / (K - 1)
-static int smooth_target(const char* what, int B, int K, float eps, float* on, float* off) {
-  if (B < 1 || K < 2) return bad_arg(what);
-  if (K > kWave || B > XENT_MAX_B) return unsupported(what);
-  if (!(eps >= 0.f && eps <= 1.f)) return bad_arg(what);
-  *on = 1.0f - eps;
-  *off = eps / (float)(K - 1);
-  return PDAE_OK;
+  return softmax_xent_grad<false>("softmax_xent_grad", B, K, 0.f, logits, labels, dloss, dlogits, stream);
 }
 
 extern "C" int pdae_softmax_xent_smooth(int B, int K, float eps, const float* logits, const int64_t* labels, float* loss,
                                         float* correct, pdae_stream_t stream) {
-  float on, off;
-  if (const int st = smooth_target("softmax_xent_smooth: B in [1, 4096], K in [2, 64] and eps in [0, 1] required", B, K,
-                                   eps, &on, &off))
-    return st;
-  if (!logits || !labels || !loss || !correct) return bad_arg("softmax_xent_smooth: null pointer");
-  hipLaunchKernelGGL(softmax_xent_smooth_kernel, dim3(1), dim3(256), 0, as_stream(stream), B, K, on, off, logits, labels,
-                     loss, correct);
-  return check_launch("softmax_xent_smooth");
+  return softmax_xent<true>("softmax_xent_smooth", B, K, eps, logits, labels, loss, correct, stream);
 }
 
 extern "C" int pdae_softmax_xent_smooth_grad(int B, int K, float eps, const float* logits, const int64_t* labels,
                                              const float* dloss, float* dlogits, pdae_stream_t stream) {
-  float on, off;
-  if (const int st = smooth_target("softmax_xent_smooth_grad: B in [1, 4096], K in [2, 64] and eps in [0, 1] required", B,
-                                   K, eps, &on, &off))
-    return st;
-  if (!logits || !labels || !dloss || !dlogits) return bad_arg("softmax_xent_smooth_grad: null pointer");
-  hipLaunchKernelGGL(softmax_xent_smooth_grad_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), B, K, on, off,
-                     logits, labels, dloss, dlogits);
-  return check_launch("softmax_xent_smooth_grad");
+  return softmax_xent_grad<true>("softmax_xent_smooth_grad", B, K, eps, logits, labels, dloss, dlogits, stream);
 }
 
 extern "C" int pdae_grad_norm_parts(long long n) {

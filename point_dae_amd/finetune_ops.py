@@ -143,13 +143,16 @@ def bn_lrelu_dropout(y, bn, p, slope, u=None, keep=None):
 
 
 class _SoftmaxXent(torch.autograd.Function):
+    """eps None: pdae_softmax_xent (one-hot target); a float: pdae_softmax_xent_smooth (label smoothing eps)."""
+
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, eps):
         B, K = logits.shape
         loss, correct = _empty((), logits), _empty((), logits)
-        _lib.call('pdae_softmax_xent', logits, B, K, _lib.ptr(logits), _lib.ptr(labels), _lib.ptr(loss),
-                  _lib.ptr(correct))
+        name, target = ('pdae_softmax_xent', ()) if eps is None else ('pdae_softmax_xent_smooth', (float(eps),))
+        _lib.call(name, logits, B, K, *target, _lib.ptr(logits), _lib.ptr(labels), _lib.ptr(loss), _lib.ptr(correct))
         ctx.save_for_backward(logits, labels)
+        ctx.name, ctx.target = name, target
         ctx.mark_non_differentiable(correct)
         return loss, correct
 
@@ -159,9 +162,9 @@ class _SoftmaxXent(torch.autograd.Function):
         B, K = logits.shape
         dloss = dloss.contiguous()
         dl = _empty((B, K), logits)
-        _lib.call('pdae_softmax_xent_grad', logits, B, K, _lib.ptr(logits), _lib.ptr(labels), _lib.ptr(dloss),
+        _lib.call(ctx.name + '_grad', logits, B, K, *ctx.target, _lib.ptr(logits), _lib.ptr(labels), _lib.ptr(dloss),
                   _lib.ptr(dl))
-        return dl, None
+        return dl, None, None
 
 
 def softmax_xent(logits, labels):
@@ -169,30 +172,7 @@ def softmax_xent(logits, labels):
     [0, K) -> (loss, correct): two device scalars, correct = the number of rows whose argmax (first on ties) is the label."""
     _gpu(logits, 'softmax_xent')
     labels = _lib.require(labels.to(torch.int64).contiguous(), 'labels', torch.int64, dim=1)
-    return _SoftmaxXent.apply(_lib.require(logits.contiguous(), 'logits', dim=2), labels)
-
-
-class _SoftmaxXentSmooth(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels, eps):
-        B, K = logits.shape
-        loss, correct = _empty((), logits), _empty((), logits)
-        _lib.call('pdae_softmax_xent_smooth', logits, B, K, float(eps), _lib.ptr(logits), _lib.ptr(labels),
-                  _lib.ptr(loss), _lib.ptr(correct))
-        ctx.save_for_backward(logits, labels)
-        ctx.eps = eps
-        ctx.mark_non_differentiable(correct)
-        return loss, correct
-
-    @staticmethod
-    def backward(ctx, dloss, _dcorrect):
-        logits, labels = ctx.saved_tensors
-        B, K = logits.shape
-        dloss = dloss.contiguous()
-        dl = _empty((B, K), logits)
-        _lib.call('pdae_softmax_xent_smooth_grad', logits, B, K, float(ctx.eps), _lib.ptr(logits), _lib.ptr(labels),
-                  _lib.ptr(dloss), _lib.ptr(dl))
-        return dl, None, None
+    return _SoftmaxXent.apply(_lib.require(logits.contiguous(), 'logits', dim=2), labels, None)
 
 
 def softmax_xent_smooth(logits, labels, eps):
@@ -203,7 +183,7 @@ def softmax_xent_smooth(logits, labels, eps):
     if not 0.0 <= float(eps) <= 1.0:
         raise ValueError(f'softmax_xent_smooth: 0 <= eps <= 1 required, got {eps}')
     labels = _lib.require(labels.to(torch.int64).contiguous(), 'labels', torch.int64, dim=1)
-    return _SoftmaxXentSmooth.apply(_lib.require(logits.contiguous(), 'logits', dim=2), labels, float(eps))
+    return _SoftmaxXent.apply(_lib.require(logits.contiguous(), 'logits', dim=2), labels, float(eps))
 
 
 class GradNormClip:

@@ -434,7 +434,46 @@ class GraphedTrainStep:
         return out
 
 
-class GraphedStaticStep:
+class _OneGraphStep:
+    """A step whose forward + loss + backward (the subclass's _fwd_bwd) is ONE captured graph, replayed every step
+    after `warmup_eager` eager steps (library init)."""
+
+    def __init__(self, model, warmup_eager):
+        assert isinstance(model, FlatDataParallel)
+        self.model = model
+        self.graph, self.out = None, None
+        _warn_if_null_stream()
+        self.eager_left = warmup_eager
+
+    def invalidate(self):
+        """Drop the captured graph (misc.BNMomentumScheduler: the momentum is a kernel argument); re-captured by the next step."""
+        self.graph, self.out = None, None
+
+    def _run(self):
+        """One eager _fwd_bwd, or the graph's replay (captured first if there is none: behind a warm-up pass on a side
+        stream, PyTorch's recipe) -> _fwd_bwd's outputs.  The bucket hooks stay out of this path (require_sync off)."""
+        sync = self.model.require_sync
+        self.model.require_sync = False
+        if self.eager_left > 0:
+            self.eager_left -= 1
+            out = self._fwd_bwd()
+        else:
+            if self.graph is None:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side), _KeepBNState(self.model.module):
+                    self._fwd_bwd()
+                torch.cuda.current_stream().wait_stream(side)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
+                    self.out = self._fwd_bwd()
+            self.graph.replay()
+            out = self.out
+        self.model.require_sync = sync
+        return out
+
+
+class GraphedStaticStep(_OneGraphStep):
     """Same idea for models whose step has static shapes and no host-side random
     draws (Point_CAE_PointNetv2: the corruption is applied by the data loader):
     ONE captured forward+loss+backward graph, replayed every step."""
@@ -444,19 +483,13 @@ class GraphedStaticStep:
         if getattr(model.module, 'draws_in_forward', False):
             raise NotImplementedError('GraphedStaticStep: this model draws a corruption on the host inside forward '
                                       '(dropout_global): a captured graph would replay one frozen draw; step it eagerly')
-        self.model, self.optimizer, self.loss_mix = model, optimizer, loss_mix
+        super().__init__(model, warmup_eager)
+        self.optimizer, self.loss_mix = optimizer, loss_mix
         dev = model.flat_param.device
         self.corrupted = torch.zeros(batch_size, npoints, 3, device=dev)
         self.clean = torch.zeros(batch_size, npoints, 3, device=dev)
-        self.graph, self.out = None, None
-        _warn_if_null_stream()
-        self.eager_left = warmup_eager
         self.spu, self.micro = int(step_per_update), 0
         self.accum = torch.zeros_like(model.flat_grad) if self.spu > 1 else None
-
-    def invalidate(self):
-        """Drop the captured graph (misc.BNMomentumScheduler: the momentum is a kernel argument); re-captured by the next step."""
-        self.graph, self.out = None, None
 
     def reset_micro(self):
         self.micro = 0
@@ -475,24 +508,7 @@ class GraphedStaticStep:
     def __call__(self, corrupted, clean):
         self.corrupted.copy_(corrupted[:, :, :3], non_blocking=True)
         self.clean.copy_(clean[:, :, :3], non_blocking=True)
-        sync = self.model.require_sync
-        self.model.require_sync = False
-        if self.eager_left > 0:
-            self.eager_left -= 1
-            out = self._fwd_bwd()
-        else:
-            if self.graph is None:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side), _KeepBNState(self.model.module):
-                    self._fwd_bwd()
-                torch.cuda.current_stream().wait_stream(side)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
-                    self.out = self._fwd_bwd()
-            self.graph.replay()
-            out = self.out
-        self.model.require_sync = sync
+        out = self._run()
         self.micro += 1
         if self.micro < self.spu:                                  # gradient-accumulation micro-step
             self.accum.add_(self.model.flat_grad)
@@ -507,7 +523,7 @@ class GraphedStaticStep:
         return out
 
 
-class GraphedClassifierStep:
+class GraphedClassifierStep(_OneGraphStep):
     """The fine-tuning step of the classifier (runner_finetune.py, point_transformer.PointTransformer): forward,
     cross-entropy, backward and -- on one process -- the gradient-norm clip coefficient captured as ONE graph, replayed
     every step.  It takes the resampled (points, labels) of a batch (the FPS + host subset draw + gather run in front
@@ -517,17 +533,11 @@ class GraphedClassifierStep:
     norm of the averaged gradient, as DistributedDataParallel + clip_grad_norm_)."""
 
     def __init__(self, model, optimizer, clip, batch_size, npoints, warmup_eager=2):
-        assert isinstance(model, FlatDataParallel)
-        self.model, self.optimizer, self.clip = model, optimizer, clip
+        super().__init__(model, warmup_eager)
+        self.optimizer, self.clip = optimizer, clip
         dev = model.flat_param.device
         self.points = torch.zeros(batch_size, npoints, 3, device=dev)
         self.labels = torch.zeros(batch_size, dtype=torch.int64, device=dev)
-        self.graph, self.out = None, None
-        _warn_if_null_stream()
-        self.eager_left = warmup_eager
-
-    def invalidate(self):
-        self.graph, self.out = None, None
 
     def _fwd_bwd(self):
         m = self.model
@@ -545,25 +555,7 @@ class GraphedClassifierStep:
     def __call__(self, points, labels):
         self.points.copy_(points[:, :, :3], non_blocking=True)
         self.labels.copy_(labels, non_blocking=True)
-        sync = self.model.require_sync
-        self.model.require_sync = False
-        if self.eager_left > 0:
-            self.eager_left -= 1
-            out = self._fwd_bwd()
-        else:
-            if self.graph is None:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side), _KeepBNState(self.model.module):
-                    self._fwd_bwd()
-                torch.cuda.current_stream().wait_stream(side)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
-                    self.out = self._fwd_bwd()
-            self.graph.replay()
-            out = self.out
-        self.model.require_sync = sync
-        loss, acc, coef = out
+        loss, acc, coef = self._run()
         if self.model.world_size > 1:
             _average_gradients(self.model)
             coef = self.clip() if self.clip is not None else None

@@ -15,28 +15,19 @@ csrc/finetune.hip (finetune_ops.py): cls token / cls position assembly, cls + ma
 -> Dropout, the softmax cross-entropy.  The head's Linear layers run on the row GEMMs (nn_ops.linear_any).  There is no
 CPU path.
 """
-import logging
-
 import torch
 import torch.nn as nn
 
 from . import finetune_ops, nn_ops
+from .classifier import Classifier
 from .point_cae_transformer import Encoder, Group, TransformerEncoder, _pos_embed, trunc_normal_
 from .registry import MODELS
 
 MAX_TOKENS = 128           # the attention kernels take T <= 128 tokens per cloud (csrc/attention.hip)
 
 
-def _missing_message(keys):
-    return 'Some model parameters or buffers are not found in the checkpoint:\n' + '\n'.join('  ' + k for k in keys)
-
-
-def _unexpected_message(keys):
-    return 'The checkpoint state_dict contains keys that are not used by the model:\n' + '\n'.join('  ' + k for k in keys)
-
-
 @MODELS.register_module()
-class PointTransformer(nn.Module):
+class PointTransformer(Classifier):
     # parameters whose gradients backward produces last (FlatDataParallel lays them at the end of the flat buffer)
     late_grad_prefixes = ('encoder.',)
 
@@ -72,78 +63,11 @@ class PointTransformer(nn.Module):
         trunc_normal_(self.cls_token, std=.02)
         trunc_normal_(self.cls_pos, std=.02)
 
-    # ---- the reference's helpers ------------------------------------------------------------------------------------
-    def get_loss_acc(self, ret, gt):
-        """nn.CrossEntropyLoss()(ret, gt) and the argmax accuracy in percent, both device scalars (Point_MAE.py:634-638)."""
-        loss, correct = finetune_ops.softmax_xent(ret, gt)
-        return loss, correct * (100.0 / gt.shape[0])
-
-    def load_model_from_ckpt(self, bert_ckpt_path, log=None):
-        """Point_MAE.py:640-676: a pretraining checkpoint with its encoder keys remapped, strict=False, the missing and
-        unexpected keys logged; None = training from scratch (trunc-normal init).  -> the incompatible-keys record
-        (None from scratch)."""
-        log = log or logging.getLogger('Transformer').info
-        if bert_ckpt_path is None:
-            log('Training from scratch!!!')
-            self.apply(self._init_weights)
-            return None
-        from .builder import remap_pretrain_keys
-        ckpt = torch.load(bert_ckpt_path, map_location='cpu')
-        incompatible = self.load_state_dict(remap_pretrain_keys(ckpt['base_model']), strict=False)
-        if incompatible.missing_keys:
-            log('missing_keys')
-            log(_missing_message(incompatible.missing_keys))
-        if incompatible.unexpected_keys:
-            log('unexpected_keys')
-            log(_unexpected_message(incompatible.unexpected_keys))
-        log(f'[Transformer] Successful Loading the ckpt from {bert_ckpt_path}')
-        return incompatible
-
-    @staticmethod
-    def _init_weights(m):              # Point_MAE.py:678-690
-        if isinstance(m, (nn.Linear, nn.Conv1d)):
-            trunc_normal_(m.weight, std=.02)
-            if m.bias is not None:
-                nn.init.constant_(m.bias, 0)
-        elif isinstance(m, nn.LayerNorm):
-            nn.init.constant_(m.bias, 0)
-            nn.init.constant_(m.weight, 1.0)
-
-    # ---- forward ----------------------------------------------------------------------------------------------------
-    def draw_dropout(self, B, device):
-        """The head's two dropout draws from ONE torch.rand launch: (u1 (B, 512), u2 (B, 256)), each contiguous
-        (graph-safe: a replay draws again from the device generator)."""
-        h = self.cls_head_finetune
-        n1, n2 = h[0].out_features, h[4].out_features
-        u = torch.rand(B * (n1 + n2), device=device)
-        return u[:B * n1].view(B, n1), u[B * n1:].view(B, n2)
-
-    def head(self, f, drop=None, drop_keep=None):
-        """cls_head_finetune on the pooled feature f (B, 2C).  drop: (u1, u2) uniforms; drop_keep: (keep1, keep2)
-        boolean keep masks (tests); neither in training mode: a fresh draw."""
-        h = self.cls_head_finetune
-        B = f.shape[0]
-        u1 = u2 = k1 = k2 = None
-        if self.training:
-            if drop_keep is not None:
-                k1, k2 = drop_keep
-            else:
-                u1, u2 = drop if drop is not None else self.draw_dropout(B, f.device)
-        x = nn_ops.linear_any(f, h[0].weight, h[0].bias)
-        x = finetune_ops.bn_relu_dropout(x, h[1], h[3].p, u=u1, keep=k1)
-        x = nn_ops.linear_any(x, h[4].weight, h[4].bias)
-        x = finetune_ops.bn_relu_dropout(x, h[5], h[7].p, u=u2, keep=k2)
-        return nn_ops.linear_any(x, h[8].weight, h[8].bias)
-
-    def forward(self, pts, drop=None, drop_keep=None, capture=None):
-        """pts (B, N, 3+) -> logits (B, cls_dim) (Point_MAE.py:692-706)."""
-        if not pts.is_cuda:
-            raise RuntimeError('PointTransformer: points must be on the GPU (there is no CPU path)')
-        pts = pts[:, :, :3].contiguous()
+    def trunk(self, pts, capture):
+        """pts (B, N, 3) -> the pooled feature (B, 2C) (Point_MAE.py:692-698)."""
         B = pts.shape[0]
         G, C = self.num_group, self.trans_dim
         T = G + 1
-        nn_ops.begin_step(pts.device)
         neighborhood, center = self.group_divider(pts)
         tokens = self.encoder(neighborhood)                                           # (B, G, C), every group
         pos = nn_ops.pos_embed(center.reshape(B * G, 3), self.pos_embed).reshape(B, G, C)
@@ -154,4 +78,4 @@ class PointTransformer(nn.Module):
         f = finetune_ops.cls_max_concat(x)                                            # (B, 2C)
         if capture is not None:
             capture.update(center=center, tokens=tokens, x=x, feature=f)
-        return self.head(f, drop, drop_keep)
+        return f

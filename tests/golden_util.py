@@ -69,3 +69,25 @@ def check_grads(model, fx, rtol, what, atol=2e-5, spike=None, max_spikes=0, name
         assert diff <= rtol * scale + atol, (what, name, diff, scale)
     assert len(spikes) <= max_spikes, (what, spikes)
     return worst
+
+
+def _rel(got, want):
+    got, want = got.detach().double().cpu(), want.detach().double().cpu()
+    return float((got - want).abs().max() / max(float(want.abs().max()), 1e-30))
+
+
+class _Without:
+    """The model's named_parameters() without the listed names (check_grads walks them)."""
+
+    def __init__(self, model, names):
+        self.model, self.names = model, set(names)
+
+    def named_parameters(self):
+        return [(n, p) for n, p in self.model.named_parameters() if n not in self.names]
+
+
+def _check_zero_grad_biases(model, ref_norms):
+    for n, ref_norm in ref_norms.items():
+        p = dict(model.named_parameters())[n]
+        got = 0.0 if p.grad is None else p.grad.double().norm().item()
+        assert got <= 1e-4 and ref_norm <= 1e-4, (n, got, ref_norm)

@@ -11,16 +11,11 @@ import numpy as np
 import pytest
 import torch
 
-from golden_util import check_grads, fill_state, load_fixture
+from golden_util import _check_zero_grad_biases, _rel, _Without, check_grads, fill_state, load_fixture
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = os.path.join(ROOT, 'cfgs', 'finetune_modelnet_dgcnn_smooth.yaml')
-
-
-def _rel(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return float((got - want).abs().max() / max(float(want.abs().max()), 1e-30))
 
 
 def _smooth_target(labels, K, eps):
@@ -185,23 +180,6 @@ def test_softmax_xent_smooth_refuses_unsupported_class_counts_and_flags_bad_labe
 # and the head's first BatchNorm removes that too.  Both sides hold rounding noise there (the reference's norms:
 # 4e-7 .. 5e-7); they are bounded on their own and left out of the relative checks
 ZERO_GRAD = ('cls_head_finetune.0.bias', 'cls_head_finetune.3.bias', 'dgcnn_encoder.bn5.bias')
-
-
-class _Without:
-    """The model's named_parameters() without the listed names (check_grads walks them)."""
-
-    def __init__(self, model, names):
-        self.model, self.names = model, set(names)
-
-    def named_parameters(self):
-        return [(n, p) for n, p in self.model.named_parameters() if n not in self.names]
-
-
-def _check_zero_grad_biases(model, ref_norms):
-    for n, ref_norm in ref_norms.items():
-        p = dict(model.named_parameters())[n]
-        got = 0.0 if p.grad is None else p.grad.double().norm().item()
-        assert got <= 1e-4 and ref_norm <= 1e-4, (n, got, ref_norm)
 
 
 def _model(seed):
