@@ -3,7 +3,7 @@ loading, weight init, the loss, and cls_head_finetune run on the HIP kernels.
 
 A subclass builds its trunk and a cls_head_finetune Sequential of Linear layers and, between them, blocks of
 BatchNorm1d -> ReLU or LeakyReLU [-> Dropout], and defines trunk(pts, capture) -> the feature the head takes.  The head's
-Linear layers run on the row GEMMs (nn_ops.linear_any), each block as ONE launch (finetune_ops.bn_relu_dropout /
+Linear layers run on the row GEMMs (rows.linear_any), each block as ONE launch (finetune_ops.bn_relu_dropout /
 bn_lrelu_dropout).  There is no CPU path.
 """
 import logging
@@ -11,8 +11,10 @@ import logging
 import torch
 import torch.nn as nn
 
-from . import finetune_ops, nn_ops
+from . import finetune_ops
+from .arena import begin_step
 from .point_cae_transformer import trunc_normal_
+from .rows import linear_any
 
 
 def _missing_message(keys):
@@ -120,7 +122,7 @@ class Classifier(nn.Module):
         x, j = f, 0
         for layer in self._head_layers():
             if isinstance(layer, nn.Linear):
-                x = nn_ops.linear_any(x, layer.weight, layer.bias)
+                x = linear_any(x, layer.weight, layer.bias)
                 continue
             bn, slope, p = layer
             u = keep = None
@@ -141,5 +143,5 @@ class Classifier(nn.Module):
         if not pts.is_cuda:
             raise RuntimeError(f'{type(self).__name__}: points must be on the GPU (there is no CPU path)')
         pts = pts[:, :, :3].contiguous()
-        nn_ops.begin_step(pts.device)
+        begin_step(pts.device)
         return self.head(self.trunk(pts, capture), drop, drop_keep)

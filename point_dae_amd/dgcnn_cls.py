@@ -11,7 +11,7 @@ unexpected, cls_head_finetune.* missing, as in the reference:
 
 The encoder is the auto-encoder's explicit kernel sequence (csrc/dgcnn.hip).  The head Linear(1024, 512) -> BatchNorm1d
 -> LeakyReLU(0.2) -> Linear(512, 256) -> BatchNorm1d -> LeakyReLU(0.2) -> Dropout(0.5) -> Linear(256, cls_dim) runs its
-Linear layers on the row GEMMs (nn_ops.linear_any) and each BatchNorm + LeakyReLU [+ Dropout] as one launch
+Linear layers on the row GEMMs (rows.linear_any) and each BatchNorm + LeakyReLU [+ Dropout] as one launch
 (finetune_ops.bn_lrelu_dropout); the loss is finetune_ops.softmax_xent_smooth (smoothloss) or softmax_xent.  There is
 no CPU path.
 """

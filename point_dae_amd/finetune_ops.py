@@ -10,10 +10,7 @@ off the GPU: there is no CPU path.
 import torch
 
 from . import _lib
-
-
-def _empty(shape, like, dtype=torch.float32):
-    return torch.empty(shape, device=like.device, dtype=dtype)
+from .rows import empty
 
 
 def _gpu(t, what):
@@ -25,7 +22,7 @@ class _PrependToken(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, token):
         B, G, C = x.shape
-        out = _empty((B, G + 1, C), x)
+        out = empty((B, G + 1, C), x)
         _lib.call('pdae_prepend_token', x, B, G, C, _lib.ptr(x), _lib.ptr(token), _lib.ptr(out))
         ctx.dims = (B, G, C)
         return out
@@ -34,7 +31,7 @@ class _PrependToken(torch.autograd.Function):
     def backward(ctx, g):
         B, G, C = ctx.dims
         g = g.contiguous()
-        dx, dtok = _empty((B, G, C), g), _empty((1, 1, C), g)
+        dx, dtok = empty((B, G, C), g), empty((1, 1, C), g)
         _lib.call('pdae_prepend_token_grad', g, B, G, C, _lib.ptr(g), _lib.ptr(dx), _lib.ptr(dtok))
         return dx, dtok
 
@@ -50,7 +47,7 @@ class _ClsMaxConcat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         B, T, C = x.shape
-        out, arg = _empty((B, 2 * C), x), _empty((B, C), x, torch.uint8)
+        out, arg = empty((B, 2 * C), x), empty((B, C), x, torch.uint8)
         _lib.call('pdae_cls_max_concat', x, B, T, C, _lib.ptr(x), _lib.ptr(out), _lib.ptr(arg))
         ctx.save_for_backward(arg)
         ctx.T = T
@@ -61,7 +58,7 @@ class _ClsMaxConcat(torch.autograd.Function):
         (arg,) = ctx.saved_tensors
         g = g.contiguous()
         B, C = arg.shape
-        dx = _empty((B, ctx.T, C), g)
+        dx = empty((B, ctx.T, C), g)
         _lib.call('pdae_cls_max_concat_grad', g, B, ctx.T, C, _lib.ptr(g), _lib.ptr(arg), _lib.ptr(dx))
         return dx
 
@@ -78,10 +75,10 @@ class _BnReluDropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, bn, training, p, u, slope=None):
         B, N = y.shape
-        out = _empty((B, N), y)
+        out = empty((B, N), y)
         mean = invstd = None
         if training:
-            mean, invstd = _empty((N,), y), _empty((N,), y)
+            mean, invstd = empty((N,), y), empty((N,), y)
         track = bn.track_running_stats
         name, act = ('pdae_bn_relu_dropout', ()) if slope is None else ('pdae_bn_lrelu_dropout', (float(slope),))
         _lib.call(name, y, B, N, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), float(bn.eps),
@@ -101,7 +98,7 @@ class _BnReluDropout(torch.autograd.Function):
         y, gamma, beta, mean, invstd, u = ctx.saved_tensors
         g = g.contiguous()
         B, N = y.shape
-        dy, dgamma, dbeta = _empty((B, N), g), _empty((N,), g), _empty((N,), g)
+        dy, dgamma, dbeta = empty((B, N), g), empty((N,), g), empty((N,), g)
         act = () if ctx.slope is None else (float(ctx.slope),)
         _lib.call('pdae_%s_grad' % what, g, B, N, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean),
                   _lib.ptr(invstd), *act, float(ctx.p), _lib.ptr(u), _lib.ptr(g), _lib.ptr(dy), _lib.ptr(dgamma),
@@ -148,7 +145,7 @@ class _SoftmaxXent(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, eps):
         B, K = logits.shape
-        loss, correct = _empty((), logits), _empty((), logits)
+        loss, correct = empty((), logits), empty((), logits)
         name, target = ('pdae_softmax_xent', ()) if eps is None else ('pdae_softmax_xent_smooth', (float(eps),))
         _lib.call(name, logits, B, K, *target, _lib.ptr(logits), _lib.ptr(labels), _lib.ptr(loss), _lib.ptr(correct))
         ctx.save_for_backward(logits, labels)
@@ -161,7 +158,7 @@ class _SoftmaxXent(torch.autograd.Function):
         logits, labels = ctx.saved_tensors
         B, K = logits.shape
         dloss = dloss.contiguous()
-        dl = _empty((B, K), logits)
+        dl = empty((B, K), logits)
         _lib.call(ctx.name + '_grad', logits, B, K, *ctx.target, _lib.ptr(logits), _lib.ptr(labels), _lib.ptr(dloss),
                   _lib.ptr(dl))
         return dl, None, None

@@ -17,7 +17,7 @@ embedder's backward -- replays; only the embedder's 2 MB are reduced in the open
 import os
 import torch
 
-from . import _lib
+from . import _lib, nn_ops
 from .corrupt_util_tensor import draw_corruption
 from .data_parallel import FlatDataParallel
 from .point_cae_transformer import draw_mask, mask_row_ids
@@ -296,7 +296,6 @@ class GraphedTrainStep:
         enc.grad_cut = cut
         # the blocks' weight gradients go straight into THIS model's flat buffer (nn_ops._sink_views): every .grad
         # is None here and nothing else touches the flat gradient views until the gather below
-        from . import nn_ops
         m.sink_armed, m.sink_written, m.sink_strided = True, set(), []
         try:
             lx, ln = m(self.pts, self.pts, steps=self.steps,

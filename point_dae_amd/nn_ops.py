@@ -1,37 +1,23 @@
-"""Dense layers of the pretraining step on flat (rows, channels) activations.
+"""Autograd glue of the Transformer and FoldingNet stages on flat (rows, channels) activations.
 
-The model code (point_cae_transformer.py, point_cae_pointnetv2.py) only calls
-the functions below.  Every dense layer runs on the hand-written gfx950 kernels:
-the Linear layers of the Transformer blocks, pos_embed and the heads on the row
-GEMM family of csrc/rows_gemm.hip (fp32 MFMA, fused bias / GELU / GELU'
-epilogues, split-K slabs, grouped weight gradients -- no BLAS library in the
-step), the patch embedder on csrc/{gemm,embed}.hip (patch_embed.py), and the
-attention core, LayerNorm with the position / residual adds, DropPath on
-csrc/{attention,block}.hip.  A whole pre-LN block is ONE autograd Function
-(_TransformerBlock) whose backward issues the data-gradient chain and then the
-block's four weight gradients as one grouped launch.
+What the model files call around the row GEMMs of rows.py, every piece on the hand-written gfx950 kernels:
+the LayerNorm / residual glue (the position and residual adds, the Linear bias and DropPath folded into the norm
+that consumes them: csrc/block.hip) and the token glue (expand_token, assemble_tokens); the DropPath draws of whole
+stacks of blocks; gelu / bias_gelu; the attention core (csrc/attention.hip); linear and conv1x1, which take the
+nn.Module; the coarse heads' mlp_chain; the FoldingNet stage (_FoldMLP, fold_mlp, _partials_sum: csrc/folding.hip);
+max_plus_mean; pos_embed; the gradient sink and the weight-gradient queue of a graphed step; and _TransformerBlock,
+a whole pre-LN block as ONE autograd Function whose backward issues the data-gradient chain and then the block's
+four weight gradients as one grouped launch.
 Parameters are read from the reference-layout nn.Modules that own them.
 """
-import ctypes
 import os
 
 import torch
-import torch.nn.functional as F
 
-from . import _lib
-from .arena import ZeroArena, arena, begin_step  # noqa: F401
-from .patch_embed import patch_embed  # noqa: F401  (fused gfx950 embedder)
-from .probe import Probe, probed_family, set_probe  # noqa: F401
-
-
-def _empty(shape, like, dtype=torch.float32):
-    return torch.empty(shape, device=like.device, dtype=dtype)
-
-
-def _colsum(x):
-    out, _ = arena.take(x.shape[1], x)
-    _lib.call('pdae_colsum', x, x.shape[0], x.shape[1], _lib.ptr(x), _lib.ptr(out), 1)
-    return out
+from . import _lib, rows
+from .arena import arena
+from .probe import Probe, probed_family, set_probe  # noqa: F401  (bench.py sets its probe through this module)
+from .rows import colsum, empty, linear_any, pad2d, rows_gemm, rows_gemm_few_rows, rows_wgrad
 
 
 class _AddLayerNorm(torch.autograd.Function):
@@ -77,7 +63,7 @@ def _from_slabs(g):
 def _add_ln_forward(x, pos, gamma, beta, eps):
     M, C = x.shape
     y = torch.empty_like(x)
-    mean, rstd = _empty((M,), x), _empty((M,), x)
+    mean, rstd = empty((M,), x), empty((M,), x)
     s = torch.empty_like(x) if pos is not None else x
     _lib.call('pdae_add_layernorm_forward', x, M, C, _lib.ptr(x), _lib.ptr(pos), _lib.ptr(gamma),
               _lib.ptr(beta), float(eps), _lib.ptr(s) if pos is not None else None, _lib.ptr(y),
@@ -121,7 +107,7 @@ def _ln_backward(dy, s, mean, rstd, gamma, dres, dacc=None, dacc_mode=0):
 def _res_ln_forward(a, bias, keep, res, pos, gamma, beta, eps, T):
     M, C = res.shape
     s, y = torch.empty_like(res), torch.empty_like(res)
-    mean, rstd = _empty((M,), res), _empty((M,), res)
+    mean, rstd = empty((M,), res), empty((M,), res)
     _lib.call('pdae_residual_layernorm_forward', res, M, C, T, _lib.ptr(a), _slabs(a), _lib.ptr(bias),
               _lib.ptr(keep), _lib.ptr(res), _lib.ptr(pos), _lib.ptr(gamma), _lib.ptr(beta), float(eps),
               _lib.ptr(s), _lib.ptr(y), _lib.ptr(mean), _lib.ptr(rstd))
@@ -172,7 +158,7 @@ class _ResidualLayerNorm(torch.autograd.Function):
                 _lib.call('pdae_scale_colsum', ds, M, C, ctx.T, _lib.ptr(ds), _lib.ptr(keep), _lib.ptr(da),
                           _lib.ptr(dbias), 1)
             else:
-                da, dbias = ds, (_colsum(ds) if ctx.has_bias else None)
+                da, dbias = ds, (colsum(ds) if ctx.has_bias else None)
             return _to_slabs(da, ctx.slabs), dbias, None, ds, (ds if ctx.has_pos else None), None, None, None, None
         dx, da, dg, db, dbias = _res_ln_backward(dy.contiguous(), s, mean, rstd, gamma, ds, keep, ctx.T)
         return (_to_slabs(da, ctx.slabs), (dbias if ctx.has_bias else None), None, dx, (dx if ctx.has_pos else None),
@@ -190,7 +176,7 @@ class _ExpandToken(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         g2 = g.reshape(-1, g.shape[-1]).contiguous()
-        return _colsum(g2).clone().reshape(1, 1, -1), None, None
+        return colsum(g2).clone().reshape(1, 1, -1), None, None
 
 
 def expand_token(token, B, M):
@@ -207,7 +193,7 @@ class _AssembleTokens(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_vis, token, B, Tv, M):
         C = x_vis.shape[-1]
-        out = _empty((B, Tv + M, C), x_vis)
+        out = empty((B, Tv + M, C), x_vis)
         _lib.call('pdae_assemble_tokens', x_vis, B, Tv + M, Tv, C, _lib.ptr(x_vis), _lib.ptr(token), _lib.ptr(out))
         ctx.dims = (B, Tv, M, C)
         return out
@@ -216,9 +202,9 @@ class _AssembleTokens(torch.autograd.Function):
     def backward(ctx, g):
         B, Tv, M, C = ctx.dims
         g = g.contiguous()
-        dvis, dmask = _empty((B, Tv, C), g), _empty((B * M, C), g)
+        dvis, dmask = empty((B, Tv, C), g), empty((B * M, C), g)
         _lib.call('pdae_assemble_tokens_grad', g, B, Tv + M, Tv, C, _lib.ptr(g), _lib.ptr(dvis), _lib.ptr(dmask))
-        return dvis, _colsum(dmask).reshape(1, 1, -1), None, None, None
+        return dvis, colsum(dmask).reshape(1, 1, -1), None, None, None
 
 
 ASSEMBLE = os.environ.get('PDAE_ASSEMBLE', os.environ.get('PDAE_GLUE', '1')) != '0'     # (A/B: 0 = torch.cat of the visible tokens and the expanded mask token)
@@ -266,8 +252,8 @@ class _Attention(torch.autograd.Function):
     def forward(ctx, qkv, B, T, H, scale):
         qkv = qkv.contiguous()
         D = qkv.shape[1] // (3 * H)
-        o = _empty((B * T, H * D), qkv)
-        lse = _empty((B, H, T), qkv)
+        o = empty((B * T, H * D), qkv)
+        lse = empty((B, H, T), qkv)
         _lib.call('pdae_attention_forward', qkv, B, T, H, D, float(scale), _lib.ptr(qkv), _lib.ptr(o),
                   _lib.ptr(lse))
         ctx.save_for_backward(qkv, o, lse)
@@ -364,7 +350,7 @@ class _ScaleResidual(torch.autograd.Function):
                       _lib.ptr(dbias), 1)
         else:
             da = dy
-            dbias = _colsum(da) if ctx.has_bias else None
+            dbias = colsum(da) if ctx.has_bias else None
         return da, dbias, None, dy, None
 
 
@@ -423,46 +409,6 @@ def stack_keeps(stack, B):
     return draw_drop_path(B, probs, stack.training, stack.dp_keep)
 
 
-def rows_gemm(x, w, w_kn=False, bias=None, epi=0, z=None, may_split=False, big_cfg=None):
-    """y = epi(x . op(w)) on the row-GEMM family (csrc/rows_gemm.hip, include/pdae.h).
-    w_kn False: w is (N, K), torch's (out, in): a Linear's forward; True: w is (K, N): the same
-    weight as the data-gradient operand.  epi 0 store (+bias) | 1 bias+ReLU | 2 GELU(z) -> y and
-    GELU'(z) -> z | 3 y = acc * z.  may_split: the result may be (S, M, N) split-K slabs whose
-    consumer adds them up (the LayerNorm kernels do)."""
-    M, K = x.shape
-    N = w.shape[1] if w_kn else w.shape[0]
-    if M * max(K, N) >= 1 << 30:             # the kernels address an operand with 32-bit byte offsets: row chunks
-        rows = ((1 << 30) // max(K, N) - 1) // 128 * 128
-        y = _empty((M, N), x)
-        for m0 in range(0, M, rows):
-            m1 = min(M, m0 + rows)
-            cfg, _, _ = _lib.rows_gemm_plan(m1 - m0, N, K, w_kn, False)
-            if big_cfg is not None and cfg < 16 and m1 - m0 >= BIG_ROWS:
-                cfg = big_cfg
-            rows_c = m1 - m0
-            probed_family('rows_gemm', 2.0 * rows_c * N * K,
-                          lambda m0=m0, m1=m1, rows_c=rows_c, cfg=cfg: _lib.call(
-                              'pdae_rows_gemm', x, rows_c, N, K, _lib.ptr(x[m0:m1]), _lib.ptr(w), int(w_kn), _lib.ptr(bias), epi,
-                              _lib.ptr(z[m0:m1]) if z is not None else None, _lib.ptr(y[m0:m1]), cfg, 1, 0),
-                          nbytes=4.0 * (rows_c * K + N * K + rows_c * N + (rows_c * N if z is not None else 0)))
-        return y
-    cfg, splits, sb = _lib.rows_gemm_plan(M, N, K, w_kn, may_split)
-    if big_cfg is not None and cfg < 16 and M >= BIG_ROWS and splits == 1:
-        cfg = big_cfg         # a caller's measured fp32-input tile shape for a multi-millisecond product (that plan is calibrated
-                              # on M <= 8192; the exact-split family's plan, cfg >= 16, prices rounds and stands)
-    y = _empty((splits, M, N) if splits > 1 else (M, N), x)
-    probed_family('rows_gemm', 2.0 * M * N * K,
-                  lambda: _lib.call('pdae_rows_gemm', x, M, N, K, _lib.ptr(x), _lib.ptr(w), int(w_kn), _lib.ptr(bias),
-                                    epi, _lib.ptr(z), _lib.ptr(y), cfg, splits, sb),
-                  nbytes=4.0 * (M * K + N * K + y.numel() + (M * N if z is not None else 0)))
-    return y
-
-
-# Tile shapes for the FoldingNet stage's multi-millisecond products (tools/lab/rows_big.py, 524288 x 512 x 512: bias+ReLU
-# forward 96x128 tiles 126.7 vs 121.9 TFLOP/s on 64x64; ReLU-masked data gradient 128x128 123.0 vs 115.7)
-BIG_ROWS = 1 << 19                 # (the published variant's 190 k-row stages are faster on the planned 64x64 tiles: 17.55 vs 17.63 ms)
-
-
 # Gradient sink.  FlatDataParallel tags every parameter it owns with (weakref to itself, index); a graphed step
 # ARMS its own FlatDataParallel instance around its forward + backward (graph_step._phase1).  A Function whose
 # weights all belong to one armed owner -- and still live in that owner's flat parameter buffer -- writes their
@@ -500,65 +446,6 @@ def flush_wgrad_queue(owner):
         owner.wgrad_queue = []
 
 
-def rows_wgrad(dys, xs, with_bias, outs=None, db_outs=None):
-    """Weight (and bias) gradients of a group of Linear layers that share their rows, one grouped
-    launch (+ the ordered slab reduction, complete when the call returns to the stream).  -> ([dW], [db or None]);
-    outs / db_outs: preallocated outputs (db_outs: one per True in with_bias), e.g. the flat gradient views of an armed
-    FlatDataParallel (_sink_views)."""
-    M = dys[0].shape[0]
-    Ns, Ks = [t.shape[1] for t in dys], [t.shape[1] for t in xs]
-    ws = _empty((max(_lib.rows_wgrad_workspace(M, Ns, Ks), 1),), dys[0])
-    dws = outs if outs is not None else [_empty((n, k), dys[0]) for n, k in zip(Ns, Ks)]
-    it = iter(db_outs) if db_outs is not None else None
-    dbs = [(next(it) if it is not None else _empty((n,), dys[0])) if f else None for n, f in zip(Ns, with_bias)]
-    probed_family('rows_wgrad', 2.0 * M * sum(n * k for n, k in zip(Ns, Ks)),
-                  lambda: _lib.rows_wgrad(dys[0], M, dys, xs, dws, dbs, ws),
-                  nbytes=4.0 * sum(M * (n + k) + n * k for n, k in zip(Ns, Ks)))
-    return dws, dbs
-
-
-class _Linear(torch.autograd.Function):
-    """y = act(x W^T + b) on rows; act None or 'relu' (the ReLU mask is recomputed from y)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, relu):
-        x = x.contiguous()
-        y = rows_gemm(x, w, False, b, 1 if relu else 0)
-        ctx.save_for_backward(x, w, y if relu else None)
-        ctx.has_bias, ctx.relu = b is not None, relu
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w, y = ctx.saved_tensors
-        dy = dy.contiguous()
-        if ctx.relu:
-            dy = dy * (y > 0)
-        dx = rows_gemm(dy, w, True) if ctx.needs_input_grad[0] else None
-        dws, dbs = rows_wgrad([dy], [x], [ctx.has_bias])
-        return dx, dws[0], dbs[0], None
-
-
-def _rows_gemm_few_rows(x, w, w_kn, bias, epi, z=None):
-    """rows_gemm for a handful of rows against a long reduction: planned with up to 8 split-K slabs, which
-    pdae_slab_sum_epi adds with the bias and the epilogue (one GEMM launch when the plan keeps one slab)."""
-    M, K = x.shape
-    N = w.shape[1] if w_kn else w.shape[0]
-    cfg, splits, sb = _lib.rows_gemm_plan(M, N, K, w_kn, 8)
-    if splits == 1:
-        return rows_gemm(x, w, w_kn, bias, epi, z)
-    slabs = _empty((splits, M, N), x)
-    y = _empty((M, N), x)
-
-    def both():                                     # the product is complete only behind the slab sum: one probed unit
-        _lib.call('pdae_rows_gemm', x, M, N, K, _lib.ptr(x), _lib.ptr(w), int(w_kn), None, 0, None,
-                  _lib.ptr(slabs), cfg, splits, sb)
-        _lib.call('pdae_slab_sum_epi', x, splits, M, N, _lib.ptr(slabs), _lib.ptr(bias), epi, _lib.ptr(z), _lib.ptr(y))
-    # bytes: operands + the slabs written by the GEMM, then the slabs read and the result written by the sum
-    probed_family('rows_gemm', 2.0 * M * N * K, both, nbytes=4.0 * (M * K + N * K + 2 * slabs.numel() + M * N))
-    return y
-
-
 class _MLPChain(torch.autograd.Function):
     """Linear -> ReLU -> Linear -> ReLU -> ... -> Linear on rows as ONE node (the coarse heads: models/PointCAE_DGCNN.py
     recfc, PointCAE_pointnetv2.py folding1, PointCAE_transformer.py coarse_pred): forward = the layers' row GEMMs with
@@ -571,7 +458,7 @@ class _MLPChain(torch.autograd.Function):
         ws, bs = params[0::2], params[1::2]
         acts = [x.contiguous()]
         for i, (w, b) in enumerate(zip(ws, bs)):
-            acts.append(_rows_gemm_few_rows(acts[-1], w, False, b, 1 if i + 1 < len(ws) else 0))
+            acts.append(rows_gemm_few_rows(acts[-1], w, False, b, 1 if i + 1 < len(ws) else 0))
         ctx.save_for_backward(*acts[:-1], *ws)
         ctx.n, ctx.has_bias = len(ws), [b is not None for b in bs]
         return acts[-1]
@@ -583,8 +470,8 @@ class _MLPChain(torch.autograd.Function):
         dys = [None] * n
         dys[n - 1] = dy.contiguous()
         for i in range(n - 1, 0, -1):                   # acts[i] = relu(layer i - 1): its sign masks the gradient
-            dys[i - 1] = _rows_gemm_few_rows(dys[i], ws[i], True, None, 4, acts[i])
-        dx = _rows_gemm_few_rows(dys[0], ws[0], True, None, 0) if ctx.needs_input_grad[0] else None
+            dys[i - 1] = rows_gemm_few_rows(dys[i], ws[i], True, None, 4, acts[i])
+        dx = rows_gemm_few_rows(dys[0], ws[0], True, None, 0) if ctx.needs_input_grad[0] else None
         dws, dbs = rows_wgrad(dys, list(acts), ctx.has_bias)
         out = [dx]
         for dw, db in zip(dws, dbs):
@@ -615,7 +502,7 @@ def _partials_sum(part):
     if not FOLD_SUMS or not part.is_cuda or part.dtype != torch.float32 or not part.is_contiguous() or part.shape[0] == 0:
         return part.sum(0)
     n = part[0].numel()
-    out = _empty(tuple(part.shape[1:]), part)
+    out = empty(tuple(part.shape[1:]), part)
     _lib.call('pdae_partials_sum_t', part, part.shape[0], 1, n, _lib.ptr(part), _lib.ptr(out))
     return out
 
@@ -635,14 +522,14 @@ class _FoldMLP(torch.autograd.Function):
     def forward(ctx, a, p, gd, row, w2, b2, w3, b3, clouds, coarse, cells):
         p = p.contiguous()
         C = p.shape[1]
-        rows = clouds * coarse * cells
+        n_rows = clouds * coarse * cells
         if row is None:
             a, gd = a.contiguous(), gd.contiguous()
-            h1 = _empty((rows, C), p)
+            h1 = empty((n_rows, C), p)
             _lib.call('pdae_fold_input', p, clouds, coarse, cells, C, _lib.ptr(a), _lib.ptr(p), _lib.ptr(gd), _lib.ptr(h1))
         else:      # a per-point term instead of the per-cloud / per-cell ones (the published variant's second stage)
             row = row.contiguous()
-            h1 = _empty((rows, C), p)
+            h1 = empty((n_rows, C), p)
             _lib.call('pdae_fold_input_rows', p, clouds * coarse, cells, C, _lib.ptr(row), _lib.ptr(p), _lib.ptr(h1))
         h2 = rows_gemm(h1, w2, False, b2, 1, big_cfg=5)
         y = rows_gemm(h2, w3, False, b3, 0)
@@ -659,7 +546,7 @@ class _FoldMLP(torch.autograd.Function):
         if w3.shape[0] == 4:
             # the C -> 3(+1) layer backwards in one pass over h2 (csrc/folding.hip fold_out_backward)
             parts = _lib.lib().pdae_fold_out_backward_parts(dy.shape[0])
-            d2, part = torch.empty_like(h2), _empty((parts, 4, C), dy)
+            d2, part = torch.empty_like(h2), empty((parts, 4, C), dy)
             _lib.call('pdae_fold_out_backward', dy, dy.shape[0], C, _lib.ptr(dy), _lib.ptr(h2), _lib.ptr(w3.contiguous()),
                       _lib.ptr(d2), _lib.ptr(part))
             dw3, db3 = _partials_sum(part), dy.sum(0)
@@ -673,13 +560,13 @@ class _FoldMLP(torch.autograd.Function):
         del d2
         if ctx.per_row:        # dp = the pairs' sums over their cells (fold_input_grad's first output; the per-cell partials unused)
             pairs = clouds * coarse
-            dp = _empty((pairs, C), dy)
-            part = _empty((_lib.lib().pdae_fold_input_grad_parts(1, pairs), cells, C), dy)
+            dp = empty((pairs, C), dy)
+            part = empty((_lib.lib().pdae_fold_input_grad_parts(1, pairs), cells, C), dy)
             _lib.call('pdae_fold_input_grad', dy, 1, pairs, cells, C, _lib.ptr(d1), _lib.ptr(dp), _lib.ptr(part))
             return None, dp, None, d1, dw2, db2, dw3, db3, None, None, None
         parts = _lib.lib().pdae_fold_input_grad_parts(clouds, coarse)
-        dp = _empty((clouds * coarse, C), dy)
-        part = _empty((parts, cells, C), dy)
+        dp = empty((clouds * coarse, C), dy)
+        part = empty((parts, cells, C), dy)
         _lib.call('pdae_fold_input_grad', dy, clouds, coarse, cells, C, _lib.ptr(d1), _lib.ptr(dp), _lib.ptr(part))
         da = dp.view(clouds, coarse, C).sum(1) if ctx.needs_input_grad[0] else None     # (a constant zero term has no gradient)
         return (da, dp, _partials_sum(part), None, dw2, db2, dw3, db3, None, None, None)
@@ -692,7 +579,7 @@ class _MaxPlusMean(torch.autograd.Function):
     def forward(ctx, x):
         x = x.contiguous()
         B, T, C = x.shape
-        out, arg = _empty((B, C), x), _empty((B, C), x, torch.uint8)
+        out, arg = empty((B, C), x), empty((B, C), x, torch.uint8)
         _lib.call('pdae_max_plus_mean', x, B, T, C, _lib.ptr(x), _lib.ptr(out), _lib.ptr(arg))
         ctx.save_for_backward(arg)
         ctx.T = T
@@ -703,129 +590,16 @@ class _MaxPlusMean(torch.autograd.Function):
         (arg,) = ctx.saved_tensors
         g = g.contiguous()
         B, C = g.shape
-        dx = _empty((B, ctx.T, C), g)
+        dx = empty((B, ctx.T, C), g)
         _lib.call('pdae_max_plus_mean_grad', g, B, ctx.T, C, _lib.ptr(g), _lib.ptr(arg), _lib.ptr(dx))
         return dx
 
 
 def max_plus_mean(x):
     """x.max(dim=1)[0] + x.mean(1) for x (B, T, C)."""
-    if not PAD2D or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3 or not 0 < x.shape[1] <= 255:
+    if not rows.PAD2D or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3 or not 0 < x.shape[1] <= 255:
         return x.max(dim=1)[0] + x.mean(1)
     return _MaxPlusMean.apply(x)
-
-
-class _SplitWeightCols(torch.autograd.Function):
-    """w (R, C) -> its column blocks [b0, b1), ... as separate contiguous operands, each zero-padded to a multiple of 4 columns
-    (one launch per block: pad2d reads the block through w's row stride); backward: the blocks' gradients side by side as dW
-    in ONE launch (csrc/glue.hip hcat) -- autograd's own path is a zero fill + a copy per block and the adds between them."""
-
-    @staticmethod
-    def forward(ctx, w, *bounds):
-        w = w.contiguous()
-        R, C = w.shape
-        outs = []
-        for b0, b1 in zip(bounds[0::2], bounds[1::2]):
-            n = b1 - b0
-            o = _empty((R, n + (-n) % 4), w)
-            _lib.call('pdae_pad2d', w, R, n, C, R, o.shape[1], w.data_ptr() + 4 * b0, _lib.ptr(o))
-            outs.append(o)
-        ctx.bounds, ctx.shape = bounds, (R, C)
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *gs):
-        R, C = ctx.shape
-        widths = [b1 - b0 for b0, b1 in zip(ctx.bounds[0::2], ctx.bounds[1::2])]
-        gs = [g.contiguous() if g is not None else None for g in gs]
-        like = next(g for g in gs if g is not None)
-        srcs = [g if g is not None else torch.zeros((R, n + (-n) % 4), device=like.device) for g, n in zip(gs, widths)]
-        k = len(srcs)
-        dw = _empty((R, C), like)
-        parr, iarr = ctypes.c_void_p * k, ctypes.c_int * k
-        _lib.call('pdae_hcat', like, k, R, parr(*[_lib.ptr(t) for t in srcs]), iarr(*widths), iarr(*[t.shape[1] for t in srcs]),
-                  _lib.ptr(dw))
-        return (dw,) + (None,) * len(ctx.bounds)
-
-
-def _hcat(pieces, R, like):
-    """pieces: [(2-D tensor or None, cols)] -> (R, sum cols) with the pieces' leading columns side by side (None: zeros)."""
-    k = len(pieces)
-    out = _empty((R, sum(c for _, c in pieces)), like)
-    parr, iarr = ctypes.c_void_p * k, ctypes.c_int * k
-    _lib.call('pdae_hcat', like, k, R, parr(*[_lib.ptr(t) for t, _ in pieces]), iarr(*[c for _, c in pieces]),
-              iarr(*[(t.stride(0) if t is not None else c) for t, c in pieces]), _lib.ptr(out))
-    return out
-
-
-class _InsertZeroCol(torch.autograd.Function):
-    """w (R, C) -> (R, C + 1) with a zero column at `at` (the pad column of a set-abstraction level's first weight: the grouped
-    rows are [xyz - centre | 0 | features]); one launch each way (was new_zeros + cat, and two slice gradients + their add)."""
-
-    @staticmethod
-    def forward(ctx, w, at):
-        w = w.contiguous()
-        R, C = w.shape
-        ctx.at, ctx.shape = at, (R, C)
-        pieces = [(w, at), (None, 1)] + ([(w[:, at:], C - at)] if C > at else [])
-        return _hcat(pieces, R, w)
-
-    @staticmethod
-    def backward(ctx, g):
-        R, C = ctx.shape
-        g = g.contiguous()
-        pieces = [(g, ctx.at)] + ([(g[:, ctx.at + 1:], C - ctx.at)] if C > ctx.at else [])
-        return _hcat(pieces, R, g), None
-
-
-def insert_zero_col(w, at):
-    if not PAD2D or not w.is_cuda or w.dtype != torch.float32 or w.dim() != 2 or not 0 < at <= w.shape[1]:
-        return torch.cat([w[:, :at], w.new_zeros(w.shape[0], 1), w[:, at:]], dim=1)
-    return _InsertZeroCol.apply(w, at)
-
-
-def split_weight_cols(w, bounds):
-    """w (R, C), bounds = [(b0, b1), ...] covering 0..C in order, at most four -> the column blocks as contiguous (R, width padded
-    to a multiple of 4) operands."""
-    flat = [v for b in bounds for v in b]
-    ok = (PAD2D and w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and 1 <= len(bounds) <= 4 and flat[0] == 0
-          and flat[-1] == w.shape[1] and all(flat[2 * i + 1] == flat[2 * i + 2] for i in range(len(bounds) - 1))
-          and all(b1 > b0 for b0, b1 in bounds))
-    if not ok:
-        return tuple(pad2d(w[:, b0:b1], 0, (-(b1 - b0)) % 4) for b0, b1 in bounds)
-    return _SplitWeightCols.apply(w, *flat)
-
-
-class _Pad2d(torch.autograd.Function):
-    """x (R, C) [or (C,)] -> (R + pr, C + pc) with zeros, one launch (csrc/glue.hip pad2d; F.pad is a fill + a copy)."""
-
-    @staticmethod
-    def forward(ctx, x, pr, pc):
-        one_d = x.dim() == 1
-        x2 = x.reshape(1, -1) if one_d else x
-        if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < x2.shape[1]):
-            x2 = x2.contiguous()                        # (a column slice of a row-major matrix is read through its row stride)
-        R, C = x2.shape
-        ld = x2.stride(0) if R > 1 else C
-        out = _empty((R + pr, C + pc), x2)
-        _lib.call('pdae_pad2d', x2, R, C, ld, R + pr, C + pc, _lib.ptr(x2), _lib.ptr(out))
-        ctx.dims = (R, C, one_d)
-        return out.reshape(-1) if one_d else out
-
-    @staticmethod
-    def backward(ctx, g):
-        R, C, one_d = ctx.dims
-        return (g[:C] if one_d else g[:R, :C]), None, None
-
-
-PAD2D = os.environ.get('PDAE_PAD2D', os.environ.get('PDAE_GLUE', '1')) != '0'
-
-
-def pad2d(x, pr, pc):
-    """zero rows below / zero columns right of a 1-D or 2-D fp32 device tensor (1-D: pc elements appended)."""
-    if not PAD2D or not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (1, 2):
-        return F.pad(x, (0, pc, 0, pr)) if x.dim() == 2 else F.pad(x, (0, pc))
-    return _Pad2d.apply(x, pr, pc)
 
 
 def fold_mlp(a, p, gd, conv2, conv3, clouds, coarse, cells, row_term=None):
@@ -841,33 +615,9 @@ def fold_mlp(a, p, gd, conv2, conv3, clouds, coarse, cells, row_term=None):
     return y[:, :n] if pn else y
 
 
-def _linear_rows(x, w, b, relu=False):
-    return linear_any(x, w, b, relu)
-
-
-def linear_any(x, w, b=None, relu=False):
-    """x W^T (+ b) (+ ReLU) for any K, N on the row GEMMs: they reduce in multiples of 4 and write
-    multiples of 4, so a ragged weight (K = 3 xyz columns, N = 3 output coordinates) is zero-padded
-    (the weight is small; an activation is padded only when it is narrow -- wide ones should be built
-    padded by the caller, as the set-abstraction grouping does)."""
-    if not (x.dim() == 2 and x.is_cuda and x.dtype == torch.float32):
-        raise RuntimeError('linear_any: rows must be a 2-D fp32 tensor on the GPU (there is no CPU / library path)')
-    N, K = w.shape
-    pk, pn = (-K) % 4, (-N) % 4
-    if pk:
-        if x.shape[1] == K:
-            x = pad2d(x, 0, pk)
-    if pk or pn:
-        w = pad2d(w, pn, pk)                            # (both paddings of the weight in one launch)
-    if pn:
-        b = pad2d(b, 0, pn) if b is not None else None
-    y = _Linear.apply(x, w, b, relu)
-    return y[:, :N] if pn else y
-
-
 def linear(x, lin, act=None):
     """nn.Linear on rows (bias, and a following ReLU, in the GEMM epilogue)."""
-    y = _linear_rows(x, lin.weight, lin.bias, act == 'relu')
+    y = linear_any(x, lin.weight, lin.bias, act == 'relu')
     if act == 'gelu':
         y = gelu(y)
     return y
@@ -875,7 +625,7 @@ def linear(x, lin, act=None):
 
 def conv1x1(x_rows, conv):
     """nn.Conv1d(kernel 1) applied to (rows, Cin) -> (rows, Cout)."""
-    return _linear_rows(x_rows, conv.weight.squeeze(-1), conv.bias)
+    return linear_any(x_rows, conv.weight.squeeze(-1), conv.bias)
 
 
 class _PosEmbed(torch.autograd.Function):
@@ -885,11 +635,11 @@ class _PosEmbed(torch.autograd.Function):
     operand); the second layer is a row GEMM.  Centres carry no gradient."""
 
     @staticmethod
-    def forward(ctx, xyz, rows, w1, b1, w2, b2):
-        M = rows.numel() if rows is not None else xyz.shape[0]
+    def forward(ctx, xyz, row_ids, w1, b1, w2, b2):
+        M = row_ids.numel() if row_ids is not None else xyz.shape[0]
         H = w1.shape[0]
-        h, gp, xp = _empty((M, H), xyz), _empty((M, H), xyz), _empty((M, 4), xyz)
-        _lib.call('pdae_pos_embed_fc1', xyz, M, H, _lib.ptr(xyz), _lib.ptr(rows), _lib.ptr(w1.contiguous()), _lib.ptr(b1),
+        h, gp, xp = empty((M, H), xyz), empty((M, H), xyz), empty((M, 4), xyz)
+        _lib.call('pdae_pos_embed_fc1', xyz, M, H, _lib.ptr(xyz), _lib.ptr(row_ids), _lib.ptr(w1.contiguous()), _lib.ptr(b1),
                   _lib.ptr(h), _lib.ptr(gp), _lib.ptr(xp))
         y = rows_gemm(h, w2, False, b2, 0)
         ctx.save_for_backward(xp, gp, h, w2)
@@ -948,15 +698,15 @@ class _TransformerBlock(torch.autograd.Function):
             x1, n1, mean1, rstd1 = _add_ln_forward(res, pos, g1, b1, eps1)
         qkv = rows_gemm(n1, wqkv)
         D = wqkv.shape[0] // (3 * H)
-        o = _empty((M, H * D), res)
-        lse = _empty((B, H, T), res)
+        o = empty((M, H * D), res)
+        lse = empty((B, H, T), res)
         _lib.call('pdae_attention_forward', qkv, B, T, H, D, float(scale), _lib.ptr(qkv), _lib.ptr(o), _lib.ptr(lse))
         if tail:
             # only the last `tail` rows of every sample are read downstream (the decoder returns the
             # masked tokens, PointCAE_transformer.py:229-231): everything after the attention core is
             # row-wise, so it runs on those rows alone.  Same values on them, zero gradient elsewhere.
             Tt = tail
-            o_t, x1_t = _empty((B * tail, H * D), res), _empty((B * tail, C), res)
+            o_t, x1_t = empty((B * tail, H * D), res), empty((B * tail, C), res)
             if H * D == C:                     # both slices in one launch (csrc/block.hip tail_rows_gather)
                 _lib.call('pdae_tail_rows_gather', res, B, T, tail, C, _lib.ptr(o), _lib.ptr(x1), _lib.ptr(o_t), _lib.ptr(x1_t))
             else:
@@ -966,7 +716,7 @@ class _TransformerBlock(torch.autograd.Function):
             Tt, o_t, x1_t = T, o, x1
         a1 = rows_gemm(o_t, wproj, may_split=True)
         x2, n2, mean2, rstd2 = _res_ln_forward(a1, bproj, keep1, x1_t, None, g2, b2, eps2, Tt)
-        gp = _empty((x2.shape[0], w1.shape[0]), res)
+        gp = empty((x2.shape[0], w1.shape[0]), res)
         h = rows_gemm(n2, w1, False, bf1, 2, gp)
         a2 = rows_gemm(h, w2, may_split=True)
         ctx.save_for_backward(x1, n1, mean1, rstd1, qkv, o, lse, x2, n2, mean2, rstd2, gp, h, keep_in, keep1,
@@ -997,9 +747,9 @@ class _TransformerBlock(torch.autograd.Function):
         o_t = o
         if tail:                               # rows outside the tail: zero gradient from this block's second half
             C = x1.shape[1]
-            o_t = _empty((B * tail, o.shape[1]), x1)
+            o_t = empty((B * tail, o.shape[1]), x1)
             _lib.call('pdae_tail_rows_gather', x1, B, T, tail, o.shape[1], _lib.ptr(o), None, _lib.ptr(o_t), None)
-            full = _empty((2, B * T, C), x1)
+            full = empty((2, B * T, C), x1)
             _lib.call('pdae_tail_rows_scatter', x1, B, T, tail, C, _lib.ptr(do), _lib.ptr(dx1), _lib.ptr(full[0]), _lib.ptr(full[1]))
             do, dx1 = full[0], full[1]
         dqkv = torch.empty_like(qkv)

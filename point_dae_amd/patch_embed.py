@@ -33,113 +33,14 @@ import torch
 from . import _lib
 from .arena import arena
 from .probe import probed, probed_family
-
-
-def _empty(shape, like, dtype=torch.float32):
-    return torch.empty(shape, device=like.device, dtype=dtype)
-
-
-def _colsum(t):
-    """Column sums (bias gradients) into a pre-zeroed arena slice."""
-    out = arena.take(t.shape[1], t)[0]
-    _lib.call('pdae_colsum', t, t.shape[0], t.shape[1], _lib.ptr(t), _lib.ptr(out), 1)
-    return out
-
-
-def _gemm(x, w, w_kn=False, bias=None):
-    """x . w^T (+ bias) with w (N, K), or x . w with w (K, N) when w_kn (csrc/rows_gemm.hip)."""
-    M, K = x.shape
-    N = w.shape[1] if w_kn else w.shape[0]
-    cfg, _, _ = _lib.rows_gemm_plan(M, N, K, w_kn, False)
-    y = _empty((M, N), x)
-    probed_family('rows_gemm', 2.0 * M * N * K,
-                  lambda: _lib.call('pdae_rows_gemm', x, M, N, K, _lib.ptr(x), _lib.ptr(w), int(w_kn), _lib.ptr(bias),
-                                    0, None, _lib.ptr(y), cfg, 1, 0), nbytes=4.0 * (M * K + N * K + M * N))
-    return y
+from .rows import bn_eval_affine, bn_finalize, colsum, empty, gemm_bnstats, linear_any, rows_gemm, rows_wgrad, wgrad_listed
 
 
 # (A/B: 0 = the small element-wise steps of the embedder as framework launches: 2 + 4 + 3 + 2 of them instead of 1 + 1 + 1 + 1)
 GLUE = os.environ.get('PDAE_EMBED_GLUE', os.environ.get('PDAE_GLUE', '1')) != '0'
 
 
-def _gemm_bnstats(dy, w, X, groups, sc, sh, mean, invstd):
-    """The data gradient dy . w (w (K, N) as stored: a conv / Linear weight (out, in)) that flows into relu(bn(X)), with the
-    ReLU mask applied and BatchNorm-backward's two column sums S (2, N) out of the same launch (csrc/rows_gemm.hip
-    pdae_rows_gemm_bnrelu_stats) -> (t, S).  X rows through `groups` (int32 list of 32-row groups) when given."""
-    M, K = dy.shape
-    N = w.shape[1]
-    t = _empty((M, N), dy)
-    S = _empty((2, N), dy)
-    ws = _empty((max(_lib.lib().pdae_rows_gemm_bnrelu_stats_workspace(M, N), 1),), dy)
-    probed_family('rows_gemm', 2.0 * M * N * K,
-                  lambda: _lib.call('pdae_rows_gemm_bnrelu_stats', dy, M, N, K, _lib.ptr(dy), _lib.ptr(w), _lib.ptr(X),
-                                    _lib.ptr(groups), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(mean), _lib.ptr(invstd),
-                                    _lib.ptr(t), _lib.ptr(S), _lib.ptr(ws)),
-                  nbytes=4.0 * (M * K + N * K + 2 * M * N))
-    return t, S
-
-
-# the embedder's own weight gradients (group-listed operands, BatchNorm + ReLU recomputed) on the grouped kernel of
-# csrc/rows_gemm.hip (ordered reduction, no atomics, no memset)
 DEBUG_KEEP = None       # (lab) a dict: the backward keeps clones of its intermediates in it (tools/lab/model_nondet.py)
-
-
-def _wgrad_listed(M, dy, a_groups, x, b_groups, scale=None, shift=None, bias=False):
-    """dW (N, K) = sum over the M listed rows of dy^T . relu(x * scale + shift) [-> (dW, column sums of dy or None)]."""
-    N, K = dy.shape[1], x.shape[1]
-    dw = _empty((N, K), x)
-    db = _empty((N,), x) if bias else None
-    ws = _empty((max(_lib.rows_wgrad_workspace(M, [N], [K]), 1),), x)
-    probed_family('rows_wgrad', 2.0 * M * N * K,
-                  lambda: _lib.call('pdae_rows_wgrad_listed', x, M, N, K, _lib.ptr(dy), _lib.ptr(a_groups), _lib.ptr(x),
-                                    _lib.ptr(b_groups), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(dw), _lib.ptr(db),
-                                    _lib.ptr(ws)), nbytes=4.0 * (M * (N + K) + N * K))
-    return dw, db
-
-
-def _wgrad(dy, x):
-    """dy^T . x on the grouped weight-gradient kernel (one problem)."""
-    M = dy.shape[0]
-    Ns, Ks = [dy.shape[1]], [x.shape[1]]
-    ws = _empty((max(_lib.rows_wgrad_workspace(M, Ns, Ks), 1),), dy)
-    dw = _empty((Ns[0], Ks[0]), dy)
-    probed_family('rows_wgrad', 2.0 * M * Ns[0] * Ks[0], lambda: _lib.rows_wgrad(dy, M, [dy], [x], [dw], [None], ws),
-                  nbytes=4.0 * (M * (Ns[0] + Ks[0]) + Ns[0] * Ks[0]))
-    return dw
-
-
-def _bn_finalize(bn, rows, like, stats64=None, partials=None):
-    """Training-mode BatchNorm bookkeeping in one launch (csrc/embed.hip bn_finalize):
-    -> scale, shift, mean, invstd; updates the running estimates and the counter."""
-    C = bn.weight.numel()
-    scale, shift, mean, invstd = (_empty((C,), like) for _ in range(4))
-    m = bn.momentum if bn.momentum is not None else 0.1
-    track = bn.track_running_stats and bn.running_mean is not None
-    _lib.call('pdae_bn_finalize', like, C, rows, _lib.ptr(stats64), _lib.ptr(partials),
-              partials.shape[0] if partials is not None else 0, _lib.ptr(bn.weight), _lib.ptr(bn.bias),
-              float(bn.eps), float(m), _lib.ptr(bn.running_mean) if track else None,
-              _lib.ptr(bn.running_var) if track else None,
-              _lib.ptr(bn.num_batches_tracked) if track else None,
-              _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd))
-    return scale, shift, mean, invstd
-
-
-def _bn_affine(bn, mean, var_biased, rows, training):
-    """scale / shift of y = x*scale + shift for this BatchNorm, plus invstd; in
-    training mode also updates the running statistics like nn.BatchNorm1d."""
-    if training:
-        invstd = torch.rsqrt(var_biased + bn.eps)
-        with torch.no_grad():
-            m = bn.momentum if bn.momentum is not None else 0.1
-            bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
-            bn.running_var.mul_(1 - m).add_(var_biased * (rows / max(rows - 1, 1)), alpha=m)
-            bn.num_batches_tracked += 1
-    else:
-        mean = bn.running_mean
-        invstd = torch.rsqrt(bn.running_var + bn.eps)
-    scale = (bn.weight * invstd).contiguous()
-    shift = (bn.bias - mean * scale).contiguous()
-    return scale, shift, mean.contiguous(), invstd.contiguous()
 
 
 # Parity-test hook (None in production): called with what decides the embedder's backward -- the BatchNorm-ReLU inputs
@@ -162,36 +63,36 @@ class PatchEmbedFunction(torch.autograd.Function):
         c1, c2, c3, c4 = w1m.shape[0], w2m.shape[0], w3m.shape[0], w4m.shape[0]
         # conv1 (K = 3) + BN1 statistics
         if training:
-            y1 = _empty((R, c1), x)
+            y1 = empty((R, c1), x)
             st1 = arena.take(4 * c1, x)[0].view(torch.float64)      # [2][c1] fp64 sums, pre-zeroed
             _lib.call('pdae_embed_conv1_stats', x, R, c1, _lib.ptr(x), _lib.ptr(w1m.contiguous()), _lib.ptr(b1),
                       _lib.ptr(y1), _lib.ptr(st1))
-            sc1, sh1, mean1, is1 = _bn_finalize(first_conv[1], R, x, stats64=st1)
+            sc1, sh1, mean1, is1 = bn_finalize(first_conv[1], R, x, stats64=st1)
         else:
-            y1 = _empty((R, c1), x)                                  # same kernel; its sums go unused in eval mode
+            y1 = empty((R, c1), x)                                  # same kernel; its sums go unused in eval mode
             st1 = torch.zeros(2 * c1, dtype=torch.float64, device=x.device)
             _lib.call('pdae_embed_conv1_stats', x, R, c1, _lib.ptr(x), _lib.ptr(w1m.contiguous()), _lib.ptr(b1),
                       _lib.ptr(y1), _lib.ptr(st1))
-            sc1, sh1, mean1, is1 = _bn_affine(first_conv[1], None, None, R, False)
+            sc1, sh1, mean1, is1 = bn_eval_affine(first_conv[1])
         # conv2: BN1+ReLU producer, store f, group max
-        f = _empty((R, c2), x)
-        g = _empty((BG, c2), x)
-        arg2 = _empty((BG, c2), x, torch.uint8)
+        f = empty((R, c2), x)
+        g = empty((BG, c2), x)
+        arg2 = empty((BG, c2), x, torch.uint8)
         probed_family('embed_gemm', 2.0 * R * c2 * c1, lambda: _lib.call(
             'pdae_embed_bnrelu_conv_store_groupmax', x, R, c2, c1, _lib.ptr(y1), _lib.ptr(sc1),
             _lib.ptr(sh1), _lib.ptr(w2m), _lib.ptr(b2), _lib.ptr(f), _lib.ptr(g), _lib.ptr(arg2)))
         # conv3 on concat([g, f]): global half once per group, local half as the GEMM
         wlt = None
         if GLUE and w3m.shape[1] == 2 * c2 and w3m.is_contiguous():
-            wg, wl = _empty((c3, c2), x), _empty((c3, c2), x)
-            wlt = _empty((c2, c3), x) if training else None         # (the backward's visible-rows data gradient reads wl^T)
+            wg, wl = empty((c3, c2), x), empty((c3, c2), x)
+            wlt = empty((c2, c3), x) if training else None         # (the backward's visible-rows data gradient reads wl^T)
             _lib.call('pdae_embed_split_conv3_weight', x, c3, c2, _lib.ptr(w3m), _lib.ptr(wg), _lib.ptr(wl), _lib.ptr(wlt))
         else:
             wg = w3m[:, :c2].contiguous()
             wl = w3m[:, c2:].contiguous()
-        gb = _gemm(g, wg, False, b3)
-        h3 = _empty((R, c3), x)
-        stats = _empty((8, 2, c3), x)
+        gb = rows_gemm(g, wg, False, b3)
+        h3 = empty((R, c3), x)
+        stats = empty((8, 2, c3), x)
         # the largest hand-written kernel of the step: bench.py's roofline kernel
         probed_family('embed_gemm', 2.0 * R * c3 * c2, lambda: probed(
             'patch_embed.second_conv[0] forward (group bias + BatchNorm statistics epilogue) %dx%dx%d' % (R, c3, c2),
@@ -199,9 +100,9 @@ class PatchEmbedFunction(torch.autograd.Function):
             lambda: _lib.call('pdae_embed_conv_groupbias_stats', x, R, c3, c2, _lib.ptr(f), _lib.ptr(wl),
                               _lib.ptr(gb), _lib.ptr(h3), _lib.ptr(stats))))
         if training:
-            sc2, sh2, mean2, is2 = _bn_finalize(second_conv[1], R, x, partials=stats)
+            sc2, sh2, mean2, is2 = bn_finalize(second_conv[1], R, x, partials=stats)
         else:
-            sc2, sh2, mean2, is2 = _bn_affine(second_conv[1], None, None, R, False)
+            sc2, sh2, mean2, is2 = bn_eval_affine(second_conv[1])
         # conv4: BN2+ReLU producer, only the group max leaves the kernel.  It comes after the
         # last BatchNorm, so it is evaluated only for the groups whose tokens are used
         # (`groups`: the visible patches; masked tokens are discarded by the caller).
@@ -215,8 +116,8 @@ class PatchEmbedFunction(torch.autograd.Function):
         else:
             Gv, inv = BG, None
         Rv = Gv * 32
-        tok = _empty((Gv, c4), x)
-        arg4 = _empty((Gv, c4), x, torch.uint8)
+        tok = empty((Gv, c4), x)
+        arg4 = empty((Gv, c4), x, torch.uint8)
         # the largest GEMM of the step: bench.py's roofline kernel
         probed_family('embed_gemm', 2.0 * Rv * c4 * c3, lambda: _lib.call(
             'pdae_embed_bnrelu_conv_groupmax', x, Rv, c4, c3, _lib.ptr(h3), _lib.ptr(sc2), _lib.ptr(sh2),
@@ -247,37 +148,38 @@ class PatchEmbedFunction(torch.autograd.Function):
         masked, gb = ctx.masked, ctx.gb
         Gv, Gm = groups.numel(), masked.numel()
         Rv, Rm, R = Gv * 32, Gm * 32, BG * 32
-        uv, dgb = _empty((2, c3), x), _empty((BG, c3), x)
+        uv, dgb = empty((2, c3), x), empty((BG, c3), x)
         # (S2: BatchNorm-2's sums, left by the GEMM that produced d3c)
         _lib.call('pdae_bnrelu_backward_listed_apply', x, BG, c3, _lib.ptr(d3c), _lib.ptr(h3), _lib.ptr(sc2), _lib.ptr(sh2),
                   _lib.ptr(mean2), _lib.ptr(is2), _lib.ptr(g2), _lib.ptr(S2), _lib.ptr(dgb), 1, _lib.ptr(uv), Gv,
                   _lib.ptr(groups))              # d3c <- dh of the visible rows; dgb[visible groups] <- their row sums
         u, v = uv[0], uv[1]
-        fsum_m = _empty((Gm, c2), x)
+        fsum_m = empty((Gm, c2), x)
         _lib.call('pdae_group_sum_listed', x, Gm, c2, _lib.ptr(f), _lib.ptr(masked), _lib.ptr(fsum_m))
         if GLUE:                                                      # xe and diag(v) W, one launch
-            xe, wv = _empty((Gm, c3), x), _empty((c3, c2), x)
+            xe, wv = empty((Gm, c3), x), empty((c3, c2), x)
             _lib.call('pdae_embed_masked_prep', x, Gm, c3, c2, _lib.ptr(uv), _lib.ptr(gb), _lib.ptr(masked), _lib.ptr(wl),
                       _lib.ptr(xe), _lib.ptr(wv))
         else:
             xe = torch.addcmul(u, gb.index_select(0, masked.long()), v)   # u + v * gb_g  (Gm, 512)
             wv = wl * v.unsqueeze(1)
         # ---- weight gradient: dW_visible + diag(v) W Gram + xe^T fsum   (u (x) sum f rides in xe)
-        dwl, _ = _wgrad_listed(Rv, d3c, None, f, groups)
-        gram, _ = _wgrad_listed(Rm, f, masked, f, masked)
-        wgram, xterm = _gemm(wl, gram), _wgrad(xe, fsum_m)            # (Gram is symmetric)
+        dwl, _ = wgrad_listed(Rv, d3c, None, f, groups)
+        gram, _ = wgrad_listed(Rm, f, masked, f, masked)
+        wgram = rows_gemm(wl, gram)                                   # (Gram is symmetric)
+        (xterm,), _ = rows_wgrad([xe], [fsum_m], [False])
         if GLUE:
             dwl = (dwl, v, wgram, xterm)                              # summed where conv3's gradient is assembled (backward)
         else:
             dwl.addcmul_(v.unsqueeze(1), wgram).add_(xterm)
         # ---- per-group sums of the masked groups (the global half of the split concat weight)
-        hs = _gemm(fsum_m, wl)                                        # the group's summed conv output, bias term apart
+        hs = rows_gemm(fsum_m, wl)                                    # the group's summed conv output, bias term apart
         _lib.call('pdae_masked_group_sums', x, Gm, c3, _lib.ptr(hs), _lib.ptr(xe), _lib.ptr(v), _lib.ptr(masked),
                   _lib.ptr(dgb))
         # ---- data gradient
-        q = _wgrad(wv, wl)                                            # W^T diag(v) W  (symmetric)
-        e = _gemm(xe, wl, True)                                       # (gb_g * v + u) W   (Gm, 256)
-        df = _empty((R, c2), x)
+        (q,), _ = rows_wgrad([wv], [wl], [False])                     # W^T diag(v) W  (symmetric)
+        e = rows_gemm(xe, wl, True)                                   # (gb_g * v + u) W   (Gm, 256)
+        df = empty((R, c2), x)
         probed_family('embed_gemm', 2.0 * Rm * c2 * c2, lambda: _lib.call(
             'pdae_group_gemm_scatter', x, Rm, c2, c2, _lib.ptr(f), _lib.ptr(masked), _lib.ptr(q), _lib.ptr(e),
             _lib.ptr(df), c2, _lib.ptr(masked)))
@@ -299,12 +201,12 @@ class PatchEmbedFunction(torch.autograd.Function):
         Gv = dtok.shape[0]                                        # groups that went through conv4
         Rv = Gv * 32
         # ---- conv4 + max-pool (compact: only the listed groups carry gradient)
-        dy4 = _empty((Rv, c4), x)
+        dy4 = empty((Rv, c4), x)
         _lib.call('pdae_group_max_scatter', x, Gv, c4, _lib.ptr(dtok), _lib.ptr(arg4), _lib.ptr(dy4))
-        db4 = _colsum(dtok)
-        dw4, _ = _wgrad_listed(Rv, dy4, None, h3, groups, sc2, sh2)
+        db4 = colsum(dtok)
+        dw4, _ = wgrad_listed(Rv, dy4, None, h3, groups, sc2, sh2)
         # (Rv, 512) grad of relu(bn2(h3)) rows, ReLU-masked, + BatchNorm-2's sums out of the same launch
-        d3c, S2 = _gemm_bnstats(dy4, w4m, h3, groups, sc2, sh2, mean2, is2)
+        d3c, S2 = gemm_bnstats(dy4, w4m, h3, groups, sc2, sh2, mean2, is2)
         del dy4
         if ctx.algebra:
             dwl, dgb, df, dbe2, dg2 = PatchEmbedFunction._masked_by_algebra(ctx, d3c, S2, f, h3, sc2, sh2, mean2, is2, g2,
@@ -312,35 +214,35 @@ class PatchEmbedFunction(torch.autograd.Function):
             del d3c
         else:
             # ---- ReLU + BN2 backward + per-group sums for the global half
-            dgb = _empty((BG, c3), x)
-            d3 = _empty((R, c3), x) if groups is not None else d3c
+            dgb = empty((BG, c3), x)
+            d3 = empty((R, c3), x) if groups is not None else d3c
             _lib.call('pdae_bnrelu_backward_apply', x, BG, c3, _lib.ptr(d3c), _lib.ptr(h3), _lib.ptr(sc2), _lib.ptr(sh2),
                       _lib.ptr(mean2), _lib.ptr(is2), _lib.ptr(g2), _lib.ptr(S2), _lib.ptr(dgb), Gv,
                       _lib.ptr(groups), _lib.ptr(inv), _lib.ptr(d3) if groups is not None else None)
             del d3c
             dbe2, dg2 = S2[0], S2[1]
             # ---- conv3 (split weight)
-            dwl = _wgrad(d3, f)          # stream-K grouped kernel, ordered reduction (no atomics)
-            df = _gemm(d3, wl, True)                                  # (R, 256)
+            (dwl,), _ = rows_wgrad([d3], [f], [False])                # stream-K grouped kernel, ordered reduction (no atomics)
+            df = rows_gemm(d3, wl, True)                              # (R, 256)
             del d3
-        dwg = _wgrad(dgb, g)
+        (dwg,), _ = rows_wgrad([dgb], [g], [False])
         # conv3's bias feeds a training-mode BatchNorm: its gradient, sum_r dy3_r, is EXACTLY zero (BatchNorm's
         # backward removes the batch mean of the gradient); the column-sum pass over dgb would only measure
         # its own rounding (the reference's value is ~1e-6 of the other gradients, noise of either sign)
         db3 = arena.take(c3, x)[0]
         if GLUE and c2 % 4 == 0:
             parts = dwl if isinstance(dwl, tuple) else (dwl, None, None, None)
-            dw3 = _empty((c3, 2 * c2, 1), x)
+            dw3 = empty((c3, 2 * c2, 1), x)
             _lib.call('pdae_embed_dw3_assemble', x, c3, c2, _lib.ptr(dwg), *[_lib.ptr(t) for t in parts], _lib.ptr(dw3))
         else:
             if isinstance(dwl, tuple):
                 dwl = dwl[0].addcmul_(dwl[1].unsqueeze(1), dwl[2]).add_(dwl[3])
             dw3 = torch.cat([dwg, dwl], dim=1).unsqueeze(-1)
-        dg = _gemm(dgb, wg, True)                                 # (BG, 256) -> arg-max rows of f
+        dg = rows_gemm(dgb, wg, True)                             # (BG, 256) -> arg-max rows of f
         _lib.call('pdae_group_scatter_add', x, BG, c2, _lib.ptr(dg), _lib.ptr(arg2), _lib.ptr(df))
         # ---- conv2
-        dw2, db2 = _wgrad_listed(R, df, None, y1, None, sc1, sh1, bias=True)    # db2: column sums of df, same kernel
-        d1, S1 = _gemm_bnstats(df, w2m, y1, None, sc1, sh1, mean1, is1)      # (R, 128), ReLU-masked, + BatchNorm-1's sums
+        dw2, db2 = wgrad_listed(R, df, None, y1, None, sc1, sh1, bias=True)    # db2: column sums of df, same kernel
+        d1, S1 = gemm_bnstats(df, w2m, y1, None, sc1, sh1, mean1, is1)      # (R, 128), ReLU-masked, + BatchNorm-1's sums
         if DEBUG_KEEP is not None:
             DEBUG_KEEP.update(df=df.clone(), d1_pre=d1.clone(), dw2=dw2.clone(), y1=y1.clone())
         del df
@@ -348,10 +250,10 @@ class PatchEmbedFunction(torch.autograd.Function):
         _lib.call('pdae_bnrelu_backward_apply', x, BG, c1, _lib.ptr(d1), _lib.ptr(y1), _lib.ptr(sc1), _lib.ptr(sh1),
                   _lib.ptr(mean1), _lib.ptr(is1), _lib.ptr(g1), _lib.ptr(S1), None, BG, None, None, None)
         dbe1, dg1 = S1[0], S1[1]
-        part1 = _empty((_lib.lib().pdae_embed_conv1_backward_weight_parts(R), 3, c1), x)
+        part1 = empty((_lib.lib().pdae_embed_conv1_backward_weight_parts(R), 3, c1), x)
         _lib.call('pdae_embed_conv1_backward_weight', x, R, c1, _lib.ptr(d1), _lib.ptr(x), _lib.ptr(part1))
         if GLUE:                                                      # (c1, 3, 1): one pass over d1, ordered partials
-            dw1 = _empty((c1, 3, 1), x)
+            dw1 = empty((c1, 3, 1), x)
             _lib.call('pdae_partials_sum_t', x, part1.shape[0], 3, c1, _lib.ptr(part1), _lib.ptr(dw1))
         else:
             dw1 = part1.sum(0).t().unsqueeze(-1)
@@ -390,18 +292,17 @@ def patch_embed_layerwise(points, first_conv, second_conv, groups=None):
     BatchNorm MODULES as they are -- which is what lets nn.SyncBatchNorm (collective C4 of SURVEY 2.2) compute its
     statistics across the replicas.  Slower than the fused path (every intermediate is materialised); used only under
     --sync_bn.  The last conv + max-pool run on the listed groups only, like the fused path."""
-    from . import nn_ops
     BG, n, _ = points.shape
     R = BG * n
-    y = nn_ops.linear_any(points.reshape(R, 3), first_conv[0].weight.squeeze(-1), first_conv[0].bias)
+    y = linear_any(points.reshape(R, 3), first_conv[0].weight.squeeze(-1), first_conv[0].bias)
     y = torch.relu(first_conv[1](y))
-    f = nn_ops.linear_any(y, first_conv[3].weight.squeeze(-1), first_conv[3].bias)
+    f = linear_any(y, first_conv[3].weight.squeeze(-1), first_conv[3].bias)
     C2 = f.shape[1]
     g = f.view(BG, n, C2).max(dim=1, keepdim=True)[0]
     cat = torch.cat([g.expand(-1, n, -1), f.view(BG, n, C2)], dim=2).reshape(R, 2 * C2)
-    h = nn_ops.linear_any(cat, second_conv[0].weight.squeeze(-1), second_conv[0].bias)
+    h = linear_any(cat, second_conv[0].weight.squeeze(-1), second_conv[0].bias)
     h = torch.relu(second_conv[1](h))
     if groups is not None:
         h = h.view(BG, n, -1).index_select(0, groups.long()).reshape(-1, h.shape[1])
-    t = nn_ops.linear_any(h, second_conv[3].weight.squeeze(-1), second_conv[3].bias)
+    t = linear_any(h, second_conv[3].weight.squeeze(-1), second_conv[3].bias)
     return t.view(-1, n, t.shape[1]).max(dim=1)[0]

@@ -26,16 +26,13 @@ import torch
 import torch.nn as nn
 
 from . import _lib, nn_ops
+from .arena import begin_step
 from .chamfer_dist import ChamferDistanceL1, ChamferDistanceL2
 from .corrupt_util_tensor import IN_FORWARD, corrupt_in_forward
-from .patch_embed import _bn_finalize
 from .registry import MODELS
+from .rows import bn_eval_affine, bn_finalize, empty, rows_gemm, rows_wgrad
 
 K_GRAPH = 20
-
-
-def _empty(shape, like, dtype=torch.float32):
-    return torch.empty(shape, device=like.device, dtype=dtype)
 
 
 def feature_knn(x_rows, B, N, k=K_GRAPH, out=None, xyz=False, pd_out=None):
@@ -46,30 +43,23 @@ def feature_knn(x_rows, B, N, k=K_GRAPH, out=None, xyz=False, pd_out=None):
     receives the -pd values that kernel selected from."""
     x = x_rows.detach()
     C = x.shape[1]
-    xx = _empty((B * N,), x)
+    xx = empty((B * N,), x)
     _lib.call('pdae_rows_sqnorm', x, B * N, C, _lib.ptr(x), _lib.ptr(xx))
-    idx = _empty((B, N, k), x, torch.int32) if out is None else out
+    idx = empty((B, N, k), x, torch.int32) if out is None else out
     if xyz:
         # the first layer's features are the points (3 coordinates + a zero column): distances straight from the rows
         if C != 4:
             raise RuntimeError('feature_knn(xyz=True): rows of 3 coordinates padded to 4 columns')
         _lib.call('pdae_xyz_topk', x, B, N, k, _lib.ptr(x), _lib.ptr(xx), _lib.ptr(idx), _lib.ptr(pd_out))
         return idx
-    gram = _empty((B, N, N), x)
+    gram = empty((B, N, N), x)
     _lib.call('pdae_rows_gemm_batched', x, B, N, N, C, _lib.ptr(x), N * C, _lib.ptr(x), N * C, _lib.ptr(gram), N * N)
     _lib.call('pdae_gram_topk', x, B, N, k, _lib.ptr(gram), _lib.ptr(xx), _lib.ptr(idx))
     return idx
 
 
 def _parts(like, width):
-    return _empty((_lib.lib().pdae_edge_parts(), 2 * width), like, torch.float64), _empty((2 * width,), like, torch.float64)
-
-
-def _eval_affine(bn):
-    """scale / shift / mean / invstd of an eval-mode BatchNorm (running estimates)."""
-    invstd = torch.rsqrt(bn.running_var + bn.eps)
-    scale = bn.weight * invstd
-    return scale, bn.bias - bn.running_mean * scale, bn.running_mean, invstd
+    return empty((_lib.lib().pdae_edge_parts(), 2 * width), like, torch.float64), empty((2 * width,), like, torch.float64)
 
 
 class _Encoder(torch.autograd.Function):
@@ -83,16 +73,16 @@ class _Encoder(torch.autograd.Function):
         convs, gammas, betas = params[0:15:3], params[1:15:3], params[2:15:3]
         k = min(K_GRAPH, N)
         cin = pts.shape[1]
-        x = _empty((R, cin + (-cin) % 4), pts)
+        x = empty((R, cin + (-cin) % 4), pts)
         _lib.call('pdae_rows_pad', pts, R, cin, x.shape[1], _lib.ptr(pts.contiguous()), _lib.ptr(x))
-        cat = _empty((R, sum(w.shape[0] for w in convs[:4])), pts)
+        cat = empty((R, sum(w.shape[0] for w in convs[:4])), pts)
         saved, off = [], 0
-        graphs = _empty((4, B, N, k), pts, torch.int32)            # the four layers' graphs: ONE reverse-graph launch backward
+        graphs = empty((4, B, N, k), pts, torch.int32)            # the four layers' graphs: ONE reverse-graph launch backward
         # the stacked weights [W1; W2 - W1] of the four layers (K padded like the layer's input rows) in one launch
         cos = [convs[li].shape[0] for li in range(4)]
         cins = [cin] + cos[:3]
         kps = [x.shape[1]] + cos[:3]
-        stacked = [_empty((2 * co, kp), x) for co, kp in zip(cos, kps)]
+        stacked = [empty((2 * co, kp), x) for co, kp in zip(cos, kps)]
         _lib.edge_weights_multi('pdae_edge_weight_stack_multi', x, cos, cins, kps, [c.contiguous() for c in convs[:4]], stacked)
         for li in range(4):
             gamma, bn = gammas[li], bns[li]
@@ -100,35 +90,35 @@ class _Encoder(torch.autograd.Function):
             assert kp == kps[li]
             w = stacked[li]
             idx = feature_knn(x, B, N, k, out=graphs[li], xyz=(li == 0 and cin == 3 and N <= 6144))
-            pq = nn_ops.rows_gemm(x, w)
-            esel, psum = _empty((R, co), x), _empty((R, co), x)
-            sel = _empty((R, co), x, torch.int16)
+            pq = rows_gemm(x, w)
+            esel, psum = empty((R, co), x), empty((R, co), x)
+            sel = empty((R, co), x, torch.int16)
             part, sums = _parts(x, co)
             _lib.call('pdae_edge_gather_stats', x, B, N, k, co, _lib.ptr(pq), _lib.ptr(idx), _lib.ptr(gamma), _lib.ptr(esel),
                       _lib.ptr(sel), _lib.ptr(psum), _lib.ptr(part), _lib.ptr(sums))
             if training:
-                scale, shift, mean, invstd = _bn_finalize(bn, R * k, x, stats64=sums)
+                scale, shift, mean, invstd = bn_finalize(bn, R * k, x, stats64=sums)
             else:
-                scale, shift, mean, invstd = (t.contiguous() for t in _eval_affine(bn))
-            out = _empty((R, co), x)
+                scale, shift, mean, invstd = bn_eval_affine(bn)
+            out = empty((R, co), x)
             _lib.call('pdae_bn_lrelu_rows', x, R, co, _lib.ptr(esel), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(out),
                       cat.data_ptr() + 4 * off, cat.shape[1])
             saved.append((x, w, idx, pq, esel, sel, psum, scale, shift, mean, invstd, cin))
             x, off, cin = out, off + co, co
         w5, g5, bn5 = convs[4].flatten(1).contiguous(), gammas[4], bns[4]
         C5 = w5.shape[0]
-        y5 = nn_ops.rows_gemm(cat, w5)
-        ysel, arow = _empty((B, C5), x), _empty((B, C5), x, torch.int32)
+        y5 = rows_gemm(cat, w5)
+        ysel, arow = empty((B, C5), x), empty((B, C5), x, torch.int32)
         rs = _lib.lib().pdae_cloud_pool_splits(B, N)
-        pv, pr = _empty((B, rs, C5), x), _empty((B, rs, C5), x, torch.int32)
-        part, sums = _empty((B * rs, 2 * C5), x, torch.float64), _empty((2 * C5,), x, torch.float64)
+        pv, pr = empty((B, rs, C5), x), empty((B, rs, C5), x, torch.int32)
+        part, sums = empty((B * rs, 2 * C5), x, torch.float64), empty((2 * C5,), x, torch.float64)
         _lib.call('pdae_cloud_pool_stats', x, B, N, C5, _lib.ptr(y5), _lib.ptr(g5), _lib.ptr(ysel), _lib.ptr(arow),
                   _lib.ptr(pv), _lib.ptr(pr), _lib.ptr(part), _lib.ptr(sums))
         if training:
-            sc5, sh5, mean5, is5 = _bn_finalize(bn5, R, x, stats64=sums)
+            sc5, sh5, mean5, is5 = bn_finalize(bn5, R, x, stats64=sums)
         else:
-            sc5, sh5, mean5, is5 = (t.contiguous() for t in _eval_affine(bn5))
-        feat = _empty((B, C5), x)
+            sc5, sh5, mean5, is5 = bn_eval_affine(bn5)
+        feat = empty((B, C5), x)
         _lib.call('pdae_bn_lrelu_rows', x, B, C5, _lib.ptr(ysel), _lib.ptr(sc5), _lib.ptr(sh5), _lib.ptr(feat), None, 0)
         ctx.layers, ctx.top, ctx.graphs = saved, (cat, w5, y5, ysel, arow, sc5, sh5, mean5, is5), graphs
         ctx.dims = (B, N, k)
@@ -144,9 +134,9 @@ class _Encoder(torch.autograd.Function):
         C5 = w5.shape[0]
         dfeat = dfeat.contiguous()
         grads = [None] * 15
-        g5 = _empty((B, C5), dfeat)
+        g5 = empty((B, C5), dfeat)
         part, sums = _parts(dfeat, C5)
-        dgamma, dbeta = _empty((C5,), dfeat), _empty((C5,), dfeat)
+        dgamma, dbeta = empty((C5,), dfeat), empty((C5,), dfeat)
         _lib.call('pdae_bn_lrelu_backward_reduce', dfeat, B, C5, _lib.ptr(dfeat), None, 0, _lib.ptr(ysel), _lib.ptr(sc5),
                   _lib.ptr(sh5), _lib.ptr(mean5), _lib.ptr(is5), _lib.ptr(g5), _lib.ptr(part), _lib.ptr(sums),
                   _lib.ptr(dgamma), _lib.ptr(dbeta))
@@ -154,40 +144,40 @@ class _Encoder(torch.autograd.Function):
             # eval-mode BatchNorm (running estimates): y = scale x + shift has no batch-statistic terms, so the c1 / c2
             # corrections of the backward kernels (fed by `sums`) vanish: d x = scale dy at the winners
             sums.zero_()
-        dy5 = _empty((R, C5), dfeat)
+        dy5 = empty((R, C5), dfeat)
         _lib.call('pdae_cloud_pool_backward', dfeat, B, N, C5, _lib.ptr(y5), _lib.ptr(g5), _lib.ptr(arow), _lib.ptr(sc5),
                   _lib.ptr(mean5), _lib.ptr(is5), _lib.ptr(sums), _lib.ptr(dy5))
-        dcat = nn_ops.rows_gemm(dy5, w5, True)
-        grads[12], grads[13], grads[14] = nn_ops.rows_wgrad([dy5], [cat], [False])[0][0].view(ctx.shapes[4]), dgamma, dbeta
+        dcat = rows_gemm(dy5, w5, True)
+        grads[12], grads[13], grads[14] = rows_wgrad([dy5], [cat], [False])[0][0].view(ctx.shapes[4]), dgamma, dbeta
         del dy5
         dx, off = None, cat.shape[1]
         # the reverse graphs (for every point the points that list it) of all four layers in one launch of 4 B blocks
-        rev_start, rev_src = _empty((4, B, N + 1), dfeat, torch.int32), _empty((4, B, N * k), dfeat, torch.int32)
+        rev_start, rev_src = empty((4, B, N + 1), dfeat, torch.int32), empty((4, B, N * k), dfeat, torch.int32)
         _lib.call('pdae_knn_reverse', dfeat, 4 * B, N, k, _lib.ptr(ctx.graphs), _lib.ptr(rev_start), _lib.ptr(rev_src))
         queue = []
         for li in (3, 2, 1, 0):
             x, w, idx, pq, esel, sel, psum, scale, shift, mean, invstd, cin = ctx.layers[li]
             co = w.shape[0] // 2
             off -= co
-            g = _empty((R, co), dfeat)
+            g = empty((R, co), dfeat)
             part, sums = _parts(dfeat, co)
-            dgamma, dbeta = _empty((co,), dfeat), _empty((co,), dfeat)
+            dgamma, dbeta = empty((co,), dfeat), empty((co,), dfeat)
             _lib.call('pdae_bn_lrelu_backward_reduce', dfeat, R, co, _lib.ptr(dx), dcat.data_ptr() + 4 * off, dcat.shape[1],
                       _lib.ptr(esel), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(g),
                       _lib.ptr(part), _lib.ptr(sums), _lib.ptr(dgamma), _lib.ptr(dbeta))
             if not ctx.training:
                 sums.zero_()
-            dpq = _empty((R, 2 * co), dfeat)
+            dpq = empty((R, 2 * co), dfeat)
             _lib.call('pdae_edge_backward', dfeat, B, N, k, co, _lib.ptr(g), _lib.ptr(pq), _lib.ptr(sel), _lib.ptr(psum),
                       _lib.ptr(rev_start[li]), _lib.ptr(rev_src[li]), _lib.ptr(scale), _lib.ptr(mean), _lib.ptr(invstd),
                       _lib.ptr(sums), _lib.ptr(dpq))
             queue.append((li, dpq, x, co, cin))
             grads[3 * li + 1], grads[3 * li + 2] = dgamma, dbeta
-            dx = nn_ops.rows_gemm(dpq, w, True) if li > 0 else None
+            dx = rows_gemm(dpq, w, True) if li > 0 else None
         # the four stacked-weight gradients [dW1; d(W2 - W1)] = dpq^T x share their rows: ONE grouped launch (+ one ordered
         # reduction) instead of four of each
-        dws = nn_ops.rows_wgrad([q[1] for q in queue], [q[2] for q in queue], [False] * len(queue))[0]
-        dconvs = [_empty(ctx.shapes[q[0]], dfeat) for q in queue]
+        dws = rows_wgrad([q[1] for q in queue], [q[2] for q in queue], [False] * len(queue))[0]
+        dconvs = [empty(ctx.shapes[q[0]], dfeat) for q in queue]
         _lib.edge_weights_multi('pdae_edge_weight_unstack_multi', dfeat, [q[3] for q in queue], [q[4] for q in queue],
                                 [q[2].shape[1] for q in queue], dws, dconvs)
         for q, dconv in zip(queue, dconvs):
@@ -249,7 +239,7 @@ class Point_CAE_DGCNN_FCOnly(nn.Module):
             raise NotImplementedError(loss_type)
 
     def forward(self, corrupted_pts, pts, vis=False, return_feat=False, capture=None, **kwargs):
-        nn_ops.begin_step(pts.device)
+        begin_step(pts.device)
         if return_feat:
             return self.dgcnn_encoder.forward_rows(pts[:, :, :3])
         corrupted_pts, pts = corrupted_pts[:, :, :3].contiguous(), pts[:, :, :3].contiguous()

@@ -26,10 +26,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, nn_ops, sa_mlp
+from .arena import begin_step
 from .chamfer_dist import ChamferDistanceL1, ChamferDistanceL2
 from .corrupt_util_tensor import corrupt_in_forward
 from .pointnet2_utils import ball_query, furthest_point_sample_with_centres
 from .registry import MODELS
+from .rows import linear_any, pad2d, split_weight_cols
 
 
 class _ConvBN(nn.Sequential):
@@ -50,7 +52,7 @@ class _ConvBN(nn.Sequential):
         w = self.conv.weight.reshape(self.conv.weight.shape[0], -1)
         if pad_at is not None:
             w = torch.cat([w[:, :pad_at], w.new_zeros(w.shape[0], 1), w[:, pad_at:]], dim=1)
-        y = nn_ops.linear_any(x, w)
+        y = linear_any(x, w)
         if isinstance(bn, nn.SyncBatchNorm):
             return F.relu(bn(y))                       # --sync_bn: the module owns the cross-replica statistics
         if self.training:
@@ -188,7 +190,7 @@ class Point_CAE_PointNetv2(nn.Module):
             raise NotImplementedError(loss_type)
 
     def forward(self, corrupted_pts, pts, vis=False, capture=None, **kwargs):
-        nn_ops.begin_step(pts.device)
+        begin_step(pts.device)
         corrupted_pts = corrupted_pts[:, :, :3].contiguous()
         pts = pts[:, :, :3].contiguous()
         # the CUDA-side dropouts of the reference's forward (:143-149); everything else came from the loader
@@ -201,10 +203,10 @@ class Point_CAE_PointNetv2(nn.Module):
         # folding2[0] on [grid(2) | coarse point(3) | global feature(1024)], split by column block
         w = self.folding2[0].weight.squeeze(-1)                                # (512, 1029)
         g2 = self.grid_size ** 2
-        wg, wc, wf = nn_ops.split_weight_cols(w, [(0, 2), (2, 5), (5, w.shape[1])])          # (narrow blocks padded to 4 columns)
-        a = nn_ops.linear_any(feature, wf, self.folding2[0].bias)                           # (B, 512)  once per cloud
-        p = nn_ops.linear_any(nn_ops.pad2d(coarse.reshape(-1, 3), 0, 1), wc).reshape(B, self.num_coarse, 1, -1)   # once per coarse point
-        gd = nn_ops.linear_any(nn_ops.pad2d(self.grid, 0, 2), wg)               # (16, 512)     once per grid cell
+        wg, wc, wf = split_weight_cols(w, [(0, 2), (2, 5), (5, w.shape[1])])                 # (narrow blocks padded to 4 columns)
+        a = linear_any(feature, wf, self.folding2[0].bias)                                  # (B, 512)  once per cloud
+        p = linear_any(pad2d(coarse.reshape(-1, 3), 0, 1), wc).reshape(B, self.num_coarse, 1, -1)                 # once per coarse point
+        gd = linear_any(pad2d(self.grid, 0, 2), wg)                             # (16, 512)     once per grid cell
         off = nn_ops.fold_mlp(a, p.reshape(B * self.num_coarse, -1), gd, self.folding2[2], self.folding2[4],
                               B, self.num_coarse, g2)
         fine = off.reshape(B, self.num_coarse, g2, 3) + coarse.unsqueeze(2)

@@ -21,11 +21,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import nn_ops
+from .arena import arena, begin_step
 from .chamfer_dist import ChamferDistanceL1, ChamferDistanceL2
 from .corrupt_util_tensor import corrupt_patches, draw_corruption
 from .knn_cuda import knn
+from .patch_embed import patch_embed
 from .pointnet2_utils import furthest_point_sample_with_centres
 from .registry import MODELS
+from .rows import linear_any, pad2d, split_weight_cols
 
 
 def trunc_normal_(tensor, mean=0., std=1., a=-2., b=2.):
@@ -49,7 +52,7 @@ class Group(nn.Module):
 
 class Encoder(nn.Module):
     """mini-PointNet patch embedder (:20-51); parameters live in the reference's
-    Sequential layout, the forward is nn_ops.patch_embed."""
+    Sequential layout, the forward is patch_embed.patch_embed."""
 
     def __init__(self, encoder_channel):
         super().__init__()
@@ -63,8 +66,7 @@ class Encoder(nn.Module):
         """(B,G,n,3) -> tokens (B,G,C); with `groups` (int32 flat group ids) only their
         tokens, as rows (len(groups), C); `masked` = the complementary list."""
         bs, g, n, _ = point_groups.shape
-        tok = nn_ops.patch_embed(point_groups.reshape(bs * g, n, 3), self.first_conv, self.second_conv,
-                                 self.training, groups, masked)
+        tok = patch_embed(point_groups.reshape(bs * g, n, 3), self.first_conv, self.second_conv, self.training, groups, masked)
         return tok if groups is not None else tok.reshape(bs, g, self.encoder_channel)
 
 
@@ -104,10 +106,6 @@ class Block(nn.Module):
         return nn_ops.transformer_block(x, pos, B, T, self, keeps, pending, pos_grad, tail)
 
 
-def _stack_keeps(stack, B):
-    return nn_ops.stack_keeps(stack, B)
-
-
 class TransformerEncoder(nn.Module):
     def __init__(self, embed_dim, depth, num_heads, drop_path_rate):
         super().__init__()
@@ -115,7 +113,7 @@ class TransformerEncoder(nn.Module):
         self.register_buffer('dp_keep', nn_ops.drop_path_keep_buffer(drop_path_rate[:depth]), persistent=False)
 
     def forward(self, x, pos, B, T):
-        keeps = _stack_keeps(self, B)
+        keeps = nn_ops.stack_keeps(self, B)
         pg = nn_ops.PosGrad(len(self.blocks))
         for i, (blk, k) in enumerate(zip(self.blocks, keeps)):   # position re-added before EVERY block (:174-177)
             x = blk(x, pos, B, T, k, pending=True, pos_grad=(pg, i))
@@ -142,7 +140,7 @@ class TransformerDecoder(nn.Module):
             nn.init.constant_(m.weight, 1.0)
 
     def forward(self, x, pos, B, T, return_token_num=-1):
-        keeps = _stack_keeps(self, B)
+        keeps = nn_ops.stack_keeps(self, B)
         pg = nn_ops.PosGrad(len(self.blocks))
         # Only the last return_token_num tokens of every sample leave the decoder (:229-231, the masked
         # ones), and after its attention core the last block is row-wise: its projection, MLP and the final
@@ -156,7 +154,7 @@ class TransformerDecoder(nn.Module):
         return nn_ops.layer_norm(x, self.norm)
 
 
-def _pos_embed(dim):
+def pos_embed_layers(dim):
     return nn.Sequential(nn.Linear(3, 128), nn.GELU(), nn.Linear(128, dim))
 
 
@@ -196,7 +194,7 @@ class MaskTransformer(nn.Module):
             raise NotImplementedError("enc_arch '3detr' is outside the pretraining hot path")
         self.mask_type = tc.mask_type
         self.encoder = Encoder(encoder_channel=self.encoder_dims)
-        self.pos_embed = _pos_embed(self.trans_dim)
+        self.pos_embed = pos_embed_layers(self.trans_dim)
         dpr = [x.item() for x in torch.linspace(0, self.drop_path_rate, self.depth)]
         self.blocks = TransformerEncoder(self.trans_dim, self.depth, self.num_heads, dpr)
         self.norm = nn.LayerNorm(self.trans_dim)
@@ -277,7 +275,7 @@ class PointCAE_transformer(nn.Module):
         self.drop_path_rate = tc.drop_path_rate
         self.mask_token = nn.Parameter(torch.zeros(1, 1, self.trans_dim))
         self.register_buffer('zero_loss', torch.zeros(1), persistent=False)      # the second loss this model returns
-        self.decoder_pos_embed = _pos_embed(self.trans_dim)
+        self.decoder_pos_embed = pos_embed_layers(self.trans_dim)
         self.decoder_depth, self.decoder_num_heads = tc.decoder_depth, tc.decoder_num_heads
         dpr = [x.item() for x in torch.linspace(0, self.drop_path_rate, self.decoder_depth)]
         self.MAE_decoder = TransformerDecoder(self.trans_dim, self.decoder_depth, self.decoder_num_heads, dpr)
@@ -301,7 +299,7 @@ class PointCAE_transformer(nn.Module):
         are compared with, and the intermediates the heads / tests need."""
         pts = pts[:, :, :3].contiguous()
         B = pts.shape[0]
-        nn_ops.begin_step(pts.device)
+        begin_step(pts.device)
         neighborhood, center = self.group_divider(pts)
         if steps is None:
             steps = draw_corruption(self.corrupt_type, B)
@@ -395,15 +393,15 @@ class PointCAE_transformer_fc_global_folding_local(PointCAE_transformer):
         C = tok.shape[1]
         w = stage[0].weight.squeeze(-1)
         # the conv's two column blocks as separate operands (the narrow one zero-padded to 4 columns), their gradients put back
-        # side by side in one launch (nn_ops.split_weight_cols)
-        wa, we = nn_ops.split_weight_cols(w, [(0, C), (C, C + extra_w_cols)])
-        a = nn_ops.linear_any(tok, wa, stage[0].bias)                                     # (P, C) once per patch
+        # side by side in one launch (rows.split_weight_cols)
+        wa, we = split_weight_cols(w, [(0, C), (C, C + extra_w_cols)])
+        a = linear_any(tok, wa, stage[0].bias)                                            # (P, C) once per patch
         xe = extra.reshape(-1, extra.shape[-1])
-        e = nn_ops.linear_any(nn_ops.pad2d(xe, 0, we.shape[1] - xe.shape[1]) if we.shape[1] != xe.shape[1] else xe, we)
+        e = linear_any(pad2d(xe, 0, we.shape[1] - xe.shape[1]) if we.shape[1] != xe.shape[1] else xe, we)
         P, cells = tok.shape[0], extra.shape[-2]
         if extra.dim() == 2:            # one term per grid cell: the fused first layer (csrc/folding.hip)
             # (no per-cloud term here: a row of the step's pre-zeroed arena, no fill launch)
-            return nn_ops.fold_mlp(nn_ops.arena.take(C, a)[0].view(1, C), a, e, stage[2], stage[4], 1, P, cells)
+            return nn_ops.fold_mlp(arena.take(C, a)[0].view(1, C), a, e, stage[2], stage[4], 1, P, cells)
         return nn_ops.fold_mlp(None, a, None, stage[2], stage[4], 1, P, cells, row_term=e)   # one term per point
 
     def forward(self, corrupted_pts, pts, vis=False, return_feat=False, mask=None, steps=None, capture=None,

@@ -12,7 +12,7 @@ unexpected keys:
 The trunk is the pretraining step's: FPS + kNN grouping, the fused patch embedder on every group, pos_embed, the pre-LN
 blocks on flat (B*T, C) rows with T = num_group + 1 (the cls token), the final LayerNorm.  Around it the glue of
 csrc/finetune.hip (finetune_ops.py): cls token / cls position assembly, cls + max pooling, the head's BatchNorm1d -> ReLU
--> Dropout, the softmax cross-entropy.  The head's Linear layers run on the row GEMMs (nn_ops.linear_any).  There is no
+-> Dropout, the softmax cross-entropy.  The head's Linear layers run on the row GEMMs (rows.linear_any).  There is no
 CPU path.
 """
 import torch
@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from . import finetune_ops, nn_ops
 from .classifier import Classifier
-from .point_cae_transformer import Encoder, Group, TransformerEncoder, _pos_embed, trunc_normal_
+from .point_cae_transformer import Encoder, Group, TransformerEncoder, pos_embed_layers, trunc_normal_
 from .registry import MODELS
 
 MAX_TOKENS = 128           # the attention kernels take T <= 128 tokens per cloud (csrc/attention.hip)
@@ -52,7 +52,7 @@ class PointTransformer(Classifier):
         self.encoder = Encoder(encoder_channel=self.encoder_dims)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, self.trans_dim))
         self.cls_pos = nn.Parameter(torch.randn(1, 1, self.trans_dim))
-        self.pos_embed = _pos_embed(self.trans_dim)
+        self.pos_embed = pos_embed_layers(self.trans_dim)
         dpr = [x.item() for x in torch.linspace(0, self.drop_path_rate, self.depth)]
         self.blocks = TransformerEncoder(self.trans_dim, self.depth, self.num_heads, dpr)
         self.norm = nn.LayerNorm(self.trans_dim)

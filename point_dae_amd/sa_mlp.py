@@ -22,7 +22,7 @@ ATen ran ~7 passes per layer forward (stats, transform, clamp) and ~6 backward.
 import torch
 
 from . import _lib
-from .patch_embed import _bn_finalize, _empty, _gemm, _gemm_bnstats, _wgrad, _wgrad_listed
+from .rows import bn_finalize, empty, gemm_bnstats, insert_zero_col, rows_gemm, rows_wgrad, wgrad_listed
 
 
 # Parity-test hook (None in production): called as ARG_HOOK(arg) with the (groups, C) uint8 winners of a level's
@@ -46,17 +46,17 @@ class SharedMLPMaxFunction(torch.autograd.Function):
         inp, sc, sh = x, None, None
         for w, bn in zip(ws, bns):
             N, K = w.shape
-            y = _empty((R, N), x)
-            stats = _empty((8, 2, N), x)
+            y = empty((R, N), x)
+            stats = empty((8, 2, N), x)
             _lib.call('pdae_conv_stats', x, R, N, K, _lib.ptr(inp), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(w),
                       _lib.ptr(y), _lib.ptr(stats))
-            sc, sh, mean, invstd = _bn_finalize(bn, R, x, partials=stats)
+            sc, sh, mean, invstd = bn_finalize(bn, R, x, partials=stats)
             ys.append(y)
             affs.append((sc, sh, mean, invstd))
             inp = y
         G, C = R // ns, ws[-1].shape[0]
-        out = _empty((G, C), x)
-        arg = _empty((G, C), x, torch.uint8)
+        out = empty((G, C), x)
+        arg = empty((G, C), x, torch.uint8)
         _lib.call('pdae_bnrelu_group_max', x, G, ns, C, _lib.ptr(inp), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(out),
                   _lib.ptr(arg))
         if ARG_HOOK is not None:
@@ -78,7 +78,7 @@ class SharedMLPMaxFunction(torch.autograd.Function):
         G, C = R // ns, ws[-1].shape[0]
         grads = [None] * (3 * nl)
         dx = None
-        d = _empty((R, C), x)
+        d = empty((R, C), x)
         dout = dout.contiguous()
         fused_pool = 256 % (C // 4) == 0 and C <= 1024
         if not fused_pool:
@@ -87,14 +87,14 @@ class SharedMLPMaxFunction(torch.autograd.Function):
         for l in range(nl - 1, -1, -1):
             sc, sh, mean, invstd = affs[l]
             N = ws[l].shape[0]
-            S = _empty((2, N), x) if S_pre is None else S_pre
+            S = empty((2, N), x) if S_pre is None else S_pre
             if S_pre is not None:
                 _lib.call('pdae_bnrelu_backward_apply', x, R // 32, N, _lib.ptr(d), _lib.ptr(ys[l]), _lib.ptr(sc),
                           _lib.ptr(sh), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(gammas[l]), _lib.ptr(S), None,
                           R // 32, None, None, None)
             elif l == nl - 1 and fused_pool:
                 # straight through the max-pool: the gradient is non-zero only at the arg-max rows
-                wsp = _empty((max(_lib.lib().pdae_pool_bn_backward_workspace(G, C), 1),), x)
+                wsp = empty((max(_lib.lib().pdae_pool_bn_backward_workspace(G, C), 1),), x)
                 _lib.call('pdae_pool_bn_backward', x, G, ns, C, _lib.ptr(dout), _lib.ptr(arg), _lib.ptr(out),
                           _lib.ptr(ys[l]), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(gammas[l]), _lib.ptr(S),
                           _lib.ptr(wsp), _lib.ptr(d))
@@ -107,14 +107,14 @@ class SharedMLPMaxFunction(torch.autograd.Function):
             if l > 0:
                 psc, psh = affs[l - 1][0], affs[l - 1][1]
                 K = ws[l].shape[1]
-                # BatchNorm + ReLU of the previous layer recomputed while its raw output is staged (patch_embed._wgrad_listed)
-                grads[3 * l] = _wgrad_listed(R, d, None, ys[l - 1], None, psc, psh)[0]
+                # BatchNorm + ReLU of the previous layer recomputed while its raw output is staged (rows.wgrad_listed)
+                grads[3 * l] = wgrad_listed(R, d, None, ys[l - 1], None, psc, psh)[0]
                 # gradient of relu(bn(y_{l-1})), ReLU-masked, + that BatchNorm's sums out of the same launch
-                d, S_pre = _gemm_bnstats(d, ws[l], ys[l - 1], None, psc, psh, affs[l - 1][2], affs[l - 1][3])
+                d, S_pre = gemm_bnstats(d, ws[l], ys[l - 1], None, psc, psh, affs[l - 1][2], affs[l - 1][3])
             else:
-                grads[0] = _wgrad(d, x)
+                (grads[0],), _ = rows_wgrad([d], [x], [False])
                 if ctx.needs_input_grad[0]:
-                    dx = _gemm(d, ws[0], True)
+                    dx = rows_gemm(d, ws[0], True)
         return (dx, None, None) + tuple(grads)
 
 
@@ -125,7 +125,6 @@ def shared_mlp_max(x, layers, ns, pad_at=None):
     for i, layer in enumerate(layers):
         w = layer.conv.weight.reshape(layer.conv.weight.shape[0], -1)
         if i == 0 and pad_at is not None:
-            from .nn_ops import insert_zero_col
             w = insert_zero_col(w, pad_at)
         bn = layer.bn.bn
         params += [w, bn.weight, bn.bias]

@@ -86,14 +86,14 @@ def test_add_layernorm(M, C, with_pos):
 
 
 def test_gelu_and_scale_residual():
-    from point_dae_amd import nn_ops
+    from point_dae_amd import arena, nn_ops
     z = torch.randn(8192, 1536, device='cuda', requires_grad=True)
     gh = torch.randn_like(z)
     h = nn_ops.gelu(z)
     h.backward(gh)
     bias = torch.randn(1536, device='cuda', requires_grad=True)
     z2 = z.detach().clone().requires_grad_(True)
-    nn_ops.begin_step(z.device)
+    arena.begin_step(z.device)
     h2 = nn_ops.bias_gelu(z2, bias)
     h2.backward(gh)
     zb = (z.detach().double() + bias.detach().double()).requires_grad_(True)
@@ -215,7 +215,7 @@ def test_colsum(M, N):
 def test_residual_layernorm_equals_unfused(B, T, C, with_keep, with_pos):
     """The fused tail (bias + DropPath + residual (+ pos) + LayerNorm, one launch each way) against
     the unfused pair scale_residual -> add_layer_norm: identical forward bits, same gradients."""
-    from point_dae_amd import nn_ops
+    from point_dae_amd import arena, nn_ops
     torch.manual_seed(B * 100 + T)
     M = B * T
     ln = torch.nn.LayerNorm(C).cuda()
@@ -231,7 +231,7 @@ def test_residual_layernorm_equals_unfused(B, T, C, with_keep, with_pos):
         a, res, bias = (t.clone().requires_grad_(True) for t in (a0, res0, bias0))
         pos = pos0.clone().requires_grad_(True) if with_pos else None
         ln.zero_grad()
-        nn_ops.begin_step(a.device)
+        arena.begin_step(a.device)
         if fused:
             s, y = nn_ops.residual_layer_norm(nn_ops.Pending(a, bias, keep, res, T), pos, ln)
         else:

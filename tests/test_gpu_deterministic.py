@@ -381,7 +381,7 @@ def test_two_threads_two_streams_two_contexts():
     and the default context is untouched.  (Forward and direct calls only: autograd runs backward nodes on ITS thread,
     which is on the default context unless told otherwise -- INTEGRATION.md.)"""
     import threading
-    from point_dae_amd import _lib, nn_ops
+    from point_dae_amd import _lib, rows
     from point_dae_amd.patch_embed import patch_embed
     first0, second0 = _embedder(1)
     torch.manual_seed(3)
@@ -404,8 +404,8 @@ def test_two_threads_two_streams_two_contexts():
                 for _ in range(rounds):
                     seen.append((_lib.deterministic(), _lib.gemm_arith(), _lib.rows_gemm_plan(3584, 1152, 384, False, False)[0] >= 16))
                     y = patch_embed(pts, first, second, True)
-                    z = nn_ops.rows_gemm(a, w)
-                    dws, dbs = nn_ops.rows_wgrad([dy], [a], [True])
+                    z = rows.rows_gemm(a, w)
+                    dws, dbs = rows.rows_wgrad([dy], [a], [True])
                 out.update(seen=seen, y=y.clone(), z=z.clone(), dw=dws[0].clone(), db=dbs[0].clone(),
                            rm=second[1].running_mean.clone())
                 stream.synchronize()

@@ -180,18 +180,18 @@ def test_a_step_with_the_single_launches_equals_the_step_with_framework_glue(mon
 @pytest.mark.parametrize('R,C,pr,pc', [(384, 3, 0, 1), (3, 384, 1, 0), (5, 6, 3, 2), (131072, 3, 0, 1)])
 def test_pad2d_and_its_gradient(R, C, pr, pc):
     import torch.nn.functional as F
-    from point_dae_amd import nn_ops
+    from point_dae_amd import rows
     x = _rand(R, C).requires_grad_(True)
-    y = nn_ops.pad2d(x, pr, pc)
+    y = rows.pad2d(x, pr, pc)
     assert torch.equal(y, F.pad(x.detach(), (0, pc, 0, pr)))
     w = _rand(R + pr, C + pc, seed=1)
     (y * w).sum().backward()
     assert torch.equal(x.grad, w[:R, :C])
     # a column slice of a wider matrix (read through its row stride) and a 1-D tensor
     wide = _rand(R, C + 5, seed=2)
-    assert torch.equal(nn_ops.pad2d(wide[:, 2:2 + C], pr, pc), F.pad(wide[:, 2:2 + C], (0, pc, 0, pr)))
+    assert torch.equal(rows.pad2d(wide[:, 2:2 + C], pr, pc), F.pad(wide[:, 2:2 + C], (0, pc, 0, pr)))
     b = _rand(C, seed=3).requires_grad_(True)
-    yb = nn_ops.pad2d(b, 0, pc)
+    yb = rows.pad2d(b, 0, pc)
     assert torch.equal(yb, F.pad(b.detach(), (0, pc)))
     yb.sum().backward()
     assert torch.equal(b.grad, torch.ones(C, device='cuda'))
@@ -215,11 +215,11 @@ def test_max_plus_mean_and_its_gradient(B, T, C):
                                       (16, [(0, 4), (4, 5), (5, 9), (9, 12)])])
 def test_split_weight_cols_and_its_gradient(R, bounds):
     import torch.nn.functional as F
-    from point_dae_amd import nn_ops
+    from point_dae_amd import rows
     C = bounds[-1][1]
     w = _rand(R, C).requires_grad_(True)
     w2 = w.detach().clone().requires_grad_(True)
-    got = nn_ops.split_weight_cols(w, bounds)
+    got = rows.split_weight_cols(w, bounds)
     want = [F.pad(w2[:, b0:b1], (0, (-(b1 - b0)) % 4)) for b0, b1 in bounds]
     loss_a = loss_b = 0
     for i, (g, x) in enumerate(zip(got, want)):
@@ -235,10 +235,10 @@ def test_split_weight_cols_and_its_gradient(R, bounds):
 
 @pytest.mark.parametrize('R,C,at', [(64, 3, 3), (128, 131, 3), (256, 259, 3), (5, 7, 2)])
 def test_insert_zero_col_and_its_gradient(R, C, at):
-    from point_dae_amd import nn_ops
+    from point_dae_amd import rows
     w = _rand(R, C).requires_grad_(True)
     w2 = w.detach().clone().requires_grad_(True)
-    got = nn_ops.insert_zero_col(w, at)
+    got = rows.insert_zero_col(w, at)
     want = torch.cat([w2[:, :at], w2.new_zeros(R, 1), w2[:, at:]], dim=1)
     assert torch.equal(got, want)
     m = _rand(R, C + 1, seed=1)

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _aggressor(side, rounds=1):
     """Enqueue `rounds` x 60 exact-split row GEMMs (2944 x 1152 x 384 and 8192 x 1536 x 384: 207 / 768 blocks of 8 waves,
     122 KB of LDS) on `side`: ~2.5 ms of bf16 MFMAs + ds_read_b128 per round on every CU."""
-    from point_dae_amd import _lib, nn_ops
+    from point_dae_amd import _lib, rows
     assert _lib.gemm_arith() == _lib.GEMM_BF16X3          # (the callers select it: the aggressor IS the exact-split GEMM)
     st = _aggressor.__dict__.setdefault('state', {})
     if not st:
@@ -37,9 +37,9 @@ def _aggressor(side, rounds=1):
     with torch.cuda.stream(side):
         for _ in range(rounds):
             for _ in range(40):
-                nn_ops.rows_gemm(st['a'], st['w'])
+                rows.rows_gemm(st['a'], st['w'])
             for _ in range(20):
-                nn_ops.rows_gemm(st['a2'], st['w2'])
+                rows.rows_gemm(st['a2'], st['w2'])
 
 
 CASES = [('tiled, 4 queries per lane (8 x 16384 x 1024)', 8, 16384, 1024, 600),

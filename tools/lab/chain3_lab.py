@@ -11,7 +11,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from point_dae_amd import _lib, nn_ops  # noqa: E402
+from point_dae_amd import _lib  # noqa: E402
+from point_dae_amd.rows import rows_gemm  # noqa: E402
 from point_dae_amd.graph_step import use_created_stream  # noqa: E402
 
 lab = ctypes.CDLL(os.path.join(ROOT, 'tools', 'lab', 'libchain3_lab.so'))
@@ -71,7 +72,7 @@ def main():
             assert rc == 0, rc
 
         def shipped():      # what the step launches today: the planned tile shapes (128 x 192 for fc1, slabs for fc2)
-            h = nn_ops.rows_gemm(X, W1)
+            h = rows_gemm(X, W1)
             cfg, splits, sb = _lib.rows_gemm_plan(M, N2, N1, False, 8)
             y = torch.empty(max(splits, 1), M, N2, device='cuda')
             _lib.call('pdae_rows_gemm', h, M, N2, N1, _lib.ptr(h), _lib.ptr(W2), 0, None, 0, None, _lib.ptr(y), cfg, splits, sb)
@@ -195,7 +196,7 @@ def main4():
             assert rc == 0, rc
 
         def shipped():
-            q = nn_ops.rows_gemm(X, Wq)
+            q = rows_gemm(X, Wq)
             outs = []
             for a, w in ((q[:, :384].contiguous() if False else q, Wp),):
                 pass
@@ -204,7 +205,7 @@ def main4():
             cfg, sp, sb = _lib.rows_gemm_plan(M, 384, 384, False, 8)
             p_ = torch.empty(max(sp, 1), M, 384, device='cuda')
             _lib.call('pdae_rows_gemm', X, M, 384, 384, _lib.ptr(X), _lib.ptr(Wp), 0, None, 0, None, _lib.ptr(p_), cfg, sp, sb)
-            h = nn_ops.rows_gemm(p_[0], W1)
+            h = rows_gemm(p_[0], W1)
             cfg, sp, sb = _lib.rows_gemm_plan(M, 384, 1536, False, 8)
             y = torch.empty(max(sp, 1), M, 384, device='cuda')
             _lib.call('pdae_rows_gemm', h, M, 384, 1536, _lib.ptr(h), _lib.ptr(W2), 0, None, 0, None, _lib.ptr(y), cfg, sp, sb)

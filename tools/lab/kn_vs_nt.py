@@ -8,7 +8,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from point_dae_amd import nn_ops  # noqa: E402
+from point_dae_amd.rows import rows_gemm  # noqa: E402
 
 
 def timed(fn, reps=60):
@@ -35,8 +35,8 @@ def main():
             dY = torch.randn(M, K, device='cuda')
             W = torch.randn(K, N, device='cuda') * K ** -0.5
             Wt = W.t().contiguous()
-            kn = lambda: nn_ops.rows_gemm(dY, W, True, may_split=split)
-            nt = lambda: nn_ops.rows_gemm(dY, Wt, False, may_split=split)
+            kn = lambda: rows_gemm(dY, W, True, may_split=split)
+            nt = lambda: rows_gemm(dY, Wt, False, may_split=split)
             a, b = kn(), nt()
             same = torch.equal(a, b) if a.shape == b.shape else 'plans differ'
             print(f"M={M} N={N} K={K} slabs={a.shape[0] if a.dim() == 3 else 1}/{b.shape[0] if b.dim() == 3 else 1}: "

@@ -9,7 +9,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from point_dae_amd import _lib, nn_ops  # noqa: E402
+from point_dae_amd import _lib  # noqa: E402
+from point_dae_amd.rows import rows_gemm  # noqa: E402
 
 lab = ctypes.CDLL(os.path.join(ROOT, 'tools', 'lab', 'libp3_lab.so'))
 vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
@@ -69,7 +70,7 @@ def main():
             row += f" gemm3 cfg{cfg} {timed(f):6.1f} |"
         ref = refs[16]
         assert torch.equal(ref, refs[18]) and torch.equal(ref, refs[19])
-        planned = lambda: nn_ops.rows_gemm(A, W, may_split=(N == 384))
+        planned = lambda: rows_gemm(A, W, may_split=(N == 384))
         row += f" planned {timed(planned):6.1f} |"
         C = torch.empty(M, N, device='cuda')
         for v in variants:

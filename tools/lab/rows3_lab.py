@@ -9,7 +9,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from point_dae_amd import _lib, nn_ops  # noqa: E402
+from point_dae_amd import _lib  # noqa: E402
+from point_dae_amd.rows import rows_gemm  # noqa: E402
 
 lab = ctypes.CDLL(os.path.join(ROOT, 'tools', 'lab', os.environ.get('LABSO', 'librows3_lab.so')))
 vp, i32 = ctypes.c_void_p, ctypes.c_int
@@ -52,7 +53,7 @@ def main():
         W = (torch.randn(K, N, device='cuda') if kn else torch.randn(N, K, device='cuda')) * K ** -0.5
         ref = A.double() @ (W.double() if kn else W.double().t())
         scale = ref.abs().max().item()
-        f32 = lambda: nn_ops.rows_gemm(A, W, w_kn=bool(kn))
+        f32 = lambda: rows_gemm(A, W, w_kn=bool(kn))
         t32 = timed(f32)
         e32 = (f32().double() - ref).abs().max().item() / scale
         row = f"{str((M, N, K)):>20} {'KN' if kn else 'NT'} | fp32 {t32:7.1f} us {e32:.1e} |"

@@ -11,7 +11,6 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from point_dae_amd import nn_ops  # noqa: E402
 from point_dae_amd.graph_step import use_created_stream  # noqa: E402
 from point_dae_amd.point_cae_transformer import Block  # noqa: E402
 
