@@ -926,6 +926,25 @@ int pdae_adamw_step_gscale(long long n, float* param, const float* grad,
                            float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                            float beta2, float eps, float weight_decay, int step,
                            const float* gscale, pdae_stream_t stream);
+/* adamw_step_segments: the same update over up to PDAE_ADAMW_MAX_SEGMENTS
+ * disjoint segments [offset, offset + count) of flat buffers of n floats, each
+ * with its own lr and weight_decay, in ONE launch.  `segments` is a HOST array:
+ * the table travels by value as a kernel argument, so a learning-rate change
+ * writes nothing to the device and the launch can be captured.  Elements
+ * outside every segment are neither read nor written.  Segments need no
+ * alignment (up to 3 head and 3 tail elements are updated one by one); the
+ * buffers are 16-byte aligned.  gscale: NULL, or adamw_step_gscale's device
+ * scalar.  Two 16-byte aligned segments give the bits of two adamw_step[_gscale]
+ * launches over the same ranges. */
+#define PDAE_ADAMW_MAX_SEGMENTS 8
+typedef struct pdae_adamw_segment {
+  long long offset, count;
+  float lr, weight_decay;
+} pdae_adamw_segment;
+int pdae_adamw_step_segments(long long n, int num_segments, const pdae_adamw_segment* segments,
+                             float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                             float beta1, float beta2, float eps, int step,
+                             const float* gscale /*nullable*/, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Classification fine-tuning glue (csrc/finetune.hip; models/Point_MAE.py:578-706
@@ -946,7 +965,15 @@ int pdae_adamw_step_gscale(long long n, float* param, const float* grad,
  *                       invstd (N) are written for the backward; an element is kept
  *                       when u (B, N uniforms; NULL = no dropout) >= p and scaled by
  *                       1/(1-p).  training == 0: the running estimates, no dropout.
+ *                       training == 2 (a frozen BatchNorm inside a model in training
+ *                       mode, set_bn_eval): the running estimates AND the draw u;
+ *                       nothing of the BatchNorm's state is written.  With training
+ *                       0 or 2, mean / invstd (nullable then) receive running_mean and
+ *                       1/sqrt(running_var + eps) for _eval_grad.
  *                       _grad (training mode): dy, dgamma, dbeta in one launch.
+ *                       _eval_grad (training 0 or 2): dy = g gamma invstd with g =
+ *                       dout * keep/(1-p) * act', dbeta = sum g, dgamma = sum g xhat
+ *                       (fp64, rows in order); B >= 1.
  *   softmax_xent        nn.CrossEntropyLoss() (mean, no smoothing) of logits (B, K)
  *                       against int64 labels in [0, K): *loss, *correct = the count of
  *                       rows whose first maximal logit is the label (float).  K <= 64,
@@ -982,6 +1009,9 @@ int pdae_bn_relu_dropout(int B, int N, const float* y, const float* gamma, const
 int pdae_bn_relu_dropout_grad(int B, int N, const float* y, const float* gamma, const float* beta, const float* mean,
                               const float* invstd, float p, const float* u /*nullable*/, const float* dout, float* dy,
                               float* dgamma, float* dbeta, pdae_stream_t stream);
+int pdae_bn_relu_dropout_eval_grad(int B, int N, const float* y, const float* gamma, const float* beta,
+                                   const float* mean, const float* invstd, float p, const float* u /*nullable*/,
+                                   const float* dout, float* dy, float* dgamma, float* dbeta, pdae_stream_t stream);
 int pdae_softmax_xent(int B, int K, const float* logits, const int64_t* labels, float* loss, float* correct,
                       pdae_stream_t stream);
 int pdae_softmax_xent_grad(int B, int K, const float* logits, const int64_t* labels, const float* dloss,
@@ -993,6 +1023,10 @@ int pdae_bn_lrelu_dropout(int B, int N, const float* y, const float* gamma, cons
 int pdae_bn_lrelu_dropout_grad(int B, int N, const float* y, const float* gamma, const float* beta, const float* mean,
                                const float* invstd, float negative_slope, float p, const float* u /*nullable*/,
                                const float* dout, float* dy, float* dgamma, float* dbeta, pdae_stream_t stream);
+int pdae_bn_lrelu_dropout_eval_grad(int B, int N, const float* y, const float* gamma, const float* beta,
+                                    const float* mean, const float* invstd, float negative_slope, float p,
+                                    const float* u /*nullable*/, const float* dout, float* dy, float* dgamma,
+                                    float* dbeta, pdae_stream_t stream);
 int pdae_softmax_xent_smooth(int B, int K, float eps, const float* logits, const int64_t* labels, float* loss,
                              float* correct, pdae_stream_t stream);
 int pdae_softmax_xent_smooth_grad(int B, int K, float eps, const float* logits, const int64_t* labels,

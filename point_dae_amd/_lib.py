@@ -141,6 +141,9 @@ _SIGNATURES = {
     "pdae_bn_lrelu_dropout_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_softmax_xent_smooth": [_i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "pdae_softmax_xent_smooth_grad": [_i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "pdae_bn_relu_dropout_eval_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_bn_lrelu_dropout_eval_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_adamw_step_segments": [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp],
     "pdae_calib_mfma_bf16": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_calib_copy": [ctypes.c_longlong, _vp, _vp, _vp],
 }
@@ -406,6 +409,30 @@ def edge_weights_multi(name, on, cos, cins, kps, srcs, dsts):
     n = len(cos)
     parr, iarr = ctypes.c_void_p * n, ctypes.c_int * n
     call(name, on, n, iarr(*cos), iarr(*cins), iarr(*kps), parr(*[ptr(t) for t in srcs]), parr(*[ptr(t) for t in dsts]))
+
+
+class AdamwSegment(ctypes.Structure):
+    """pdae_adamw_segment of include/pdae.h."""
+    _fields_ = [('offset', ctypes.c_longlong), ('count', ctypes.c_longlong), ('lr', ctypes.c_float),
+                ('weight_decay', ctypes.c_float)]
+
+
+ADAMW_MAX_SEGMENTS = 8
+
+
+def adamw_step_segments(flat_param, flat_grad, exp_avg, exp_avg_sq, segments, beta1, beta2, eps, step, gscale=None):
+    """pdae_adamw_step_segments: segments = [(offset, count, lr, weight_decay)] over the flat buffers, 8 per launch
+    (longer lists are cut); gscale: None or a one-element device tensor."""
+    for t in (flat_grad, exp_avg, exp_avg_sq):
+        if t.numel() != flat_param.numel():
+            raise ValueError('adamw_step_segments: the four flat buffers must have one length')
+        require(t, 'adamw_step_segments buffer', dim=1)
+    require(flat_param, 'flat_param', dim=1)
+    for i in range(0, len(segments), ADAMW_MAX_SEGMENTS):
+        part = segments[i:i + ADAMW_MAX_SEGMENTS]
+        table = (AdamwSegment * len(part))(*[AdamwSegment(int(o), int(c), float(lr), float(wd)) for o, c, lr, wd in part])
+        call('pdae_adamw_step_segments', flat_param, flat_param.numel(), len(part), table, ptr(flat_param), ptr(flat_grad),
+             ptr(exp_avg), ptr(exp_avg_sq), float(beta1), float(beta2), float(eps), int(step), ptr(gscale))
 
 
 WGRAD_MULTI_MAX = 48

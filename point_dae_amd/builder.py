@@ -21,7 +21,10 @@ def _unwrap(model):
 
 def add_weight_decay(model, weight_decay, part='all', lr=None, skip_list=()):
     """AdamW parameter groups (builder.py:41-98): 1-D tensors, '.bias' and names
-    containing 'token' get no weight decay."""
+    containing 'token' get no weight decay.  part 'diff_lr' is the reference's as it runs: the pretrained parameters
+    (no 'cls' in the name) form two groups at 0.1 x lr; the new ones are sorted into lists the reference never hands
+    to the optimiser (:57-61 fill no_decay_new / decay_new, :88-89 return the empty no_decay / decay), so the last
+    two groups are empty and cls_token, cls_pos and cls_head_finetune keep their initial values."""
     def no_wd(name, p):
         return p.dim() == 1 or name.endswith('.bias') or 'token' in name or name in skip_list
 
@@ -40,11 +43,14 @@ def add_weight_decay(model, weight_decay, part='all', lr=None, skip_list=()):
     for name, p in _unwrap(model).named_parameters():
         if not p.requires_grad or not chosen(name):
             continue
-        pre = part == 'diff_lr' and 'cls' not in name
-        if no_wd(name, p):
-            (no_decay_pre if pre else no_decay).append(p)
+        if part == 'diff_lr':
+            if 'cls' in name:
+                continue                    # (the reference's no_decay_new / decay_new: in no returned group)
+            (no_decay_pre if no_wd(name, p) else decay_pre).append(p)
+        elif no_wd(name, p):
+            no_decay.append(p)
         else:
-            (decay_pre if pre else decay).append(p)
+            decay.append(p)
     groups = []
     if part == 'diff_lr':
         groups += [{'params': no_decay_pre, 'weight_decay': 0., 'lr': lr * 0.1},
@@ -95,9 +101,10 @@ def build_opti_sche(base_model, config):
         raise NotImplementedError(oc.type)
     from .data_parallel import FlatDataParallel
     if (isinstance(base_model, FlatDataParallel) and base_model.flat_param.is_cuda
-            and oc.get('part', 'all') == 'all'):
-        from .optim import FlatAdamW            # two fused launches over the flat buffers
-        optimizer = FlatAdamW(base_model, **oc.kwargs)
+            and oc.get('part', 'all') in ('all', 'only_new', 'diff_lr')):
+        # two fused launches over the flat buffers (all), or one segmented launch over the groups' runs in them
+        from .optim import FlatAdamW
+        optimizer = FlatAdamW(base_model, part=oc.get('part', 'all'), **oc.kwargs)
     else:
         groups = add_weight_decay(base_model, oc.kwargs.weight_decay, part=oc.get('part', 'all'), lr=oc.kwargs.lr)
         optimizer = torch.optim.AdamW(groups, **oc.kwargs)

@@ -33,6 +33,9 @@ def _per_dropout(t):
 class Classifier(nn.Module):
     # the label smoothing eps of get_loss_acc; None: plain cross-entropy
     smooth_eps = None
+    # None, or why the model cannot train under optimizer.part only_new (runner_finetune.set_bn_eval freezes a part of
+    # its BatchNorms): the text of the NotImplementedError runner_finetune raises
+    only_new_unsupported = None
 
     # ---- the reference's helpers ------------------------------------------------------------------------------------
     def get_loss_acc(self, ret, gt):
@@ -133,9 +136,9 @@ class Classifier(nn.Module):
                 keep = keeps[j] if keeps is not None else None
                 j += 1
             if slope is None:
-                x = finetune_ops.bn_relu_dropout(x, bn, p, u=u, keep=keep)
+                x = finetune_ops.bn_relu_dropout(x, bn, p, u=u, keep=keep, dropout=self.training)
             else:
-                x = finetune_ops.bn_lrelu_dropout(x, bn, p, slope, u=u, keep=keep)
+                x = finetune_ops.bn_lrelu_dropout(x, bn, p, slope, u=u, keep=keep, dropout=self.training)
         return x
 
     def forward(self, pts, drop=None, drop_keep=None, capture=None):

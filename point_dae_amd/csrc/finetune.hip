@@ -6,6 +6,7 @@
 //   pdae_bn_relu_dropout / _grad  Linear -> BatchNorm1d -> ReLU -> Dropout(p) of cls_head_finetune (:616-626) after its
 //                                 Linear: batch statistics, running estimates, the affine, ReLU and the dropout mask in
 //                                 ONE launch (a thread owns a column and walks the B rows), backward likewise
+//                                 _eval_grad: the backward on the running estimates (a frozen BatchNorm, training 0 / 2)
 //   pdae_bn_lrelu_dropout / _grad the same for DGCNN's head (models/PointCAE_DGCNN.py:572-663): BatchNorm1d ->
 //                                 LeakyReLU(slope) -> Dropout(p); at slope 0 it gives bn_relu_dropout's bits.  Both
 //                                 entries launch bn_act_dropout_kernel / _grad_kernel, templated on the activation
@@ -89,7 +90,9 @@ __global__ __launch_bounds__(256) void cls_max_concat_grad_kernel(long long n, i
 
 // thread per column n of y (B, N).  Training: fp64 mean and biased variance over the B rows (two passes), the running
 // estimates with the unbiased variance (nn.BatchNorm1d), mean / invstd saved for the backward; eval: the running
-// estimates.  out = act((y - mean) gamma invstd + beta) * (u >= p ? 1 / (1 - p) : 0); u null: no dropout.
+// estimates, also written to mean / invstd when those are given (the eval-mode backward reads them); the host passes u
+// in eval mode only for a frozen BatchNorm under a live Dropout (the entry's training = 2).
+// out = act((y - mean) gamma invstd + beta) * (u >= p ? 1 / (1 - p) : 0); u null: no dropout.
 // act = relu, or (LEAKY) LeakyReLU: max(v, 0) + slope min(v, 0) -- one of the two terms is 0, so it is torch's
 // `v > 0 ? v : v * slope` with a +0 (never -0) for v <= 0 at slope 0, as fmaxf(v, 0) gives.  The two activations keep
 // separate expressions: LEAKY at slope 0 gives the ReLU instantiation's bits through that signed-zero argument
@@ -124,6 +127,8 @@ __global__ __launch_bounds__(256) void bn_act_dropout_kernel(int B, int N, const
   } else {
     m = rmean[n];
     is = 1.0f / sqrtf(rvar[n] + eps);
+    if (mean) mean[n] = m;                            // (for the eval-mode backward)
+    if (invstd) invstd[n] = is;
   }
   const float sc = gamma[n] * is, be = beta[n];
   const float keep_scale = 1.0f / (1.0f - p);
@@ -146,9 +151,10 @@ __device__ __forceinline__ float act_grad(float z, const float* __restrict__ dou
   else return z > 0.f ? *dout : 0.f;
 }
 
-// backward of the training-mode forward, thread per column: g = dout * dropout mask * act'(.); dbeta = sum g,
-// dgamma = sum g xhat (fp64, rows in order); dy = gamma invstd (g - dbeta / B - xhat dgamma / B)
-template <bool LEAKY>
+// backward of the forward, thread per column: g = dout * dropout mask * act'(.); dbeta = sum g,
+// dgamma = sum g xhat (fp64, rows in order); BATCH (training-mode BatchNorm): dy = gamma invstd (g - dbeta / B -
+// xhat dgamma / B); else (the running estimates: mean and invstd are constants) dy = gamma invstd g
+template <bool LEAKY, bool BATCH>
 __global__ __launch_bounds__(256) void bn_act_dropout_grad_kernel(int B, int N, const float* __restrict__ y,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                   const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -177,7 +183,8 @@ __global__ __launch_bounds__(256) void bn_act_dropout_grad_kernel(int B, int N, 
     const float x = y[k];
     float g = act_grad<LEAKY>((x - m) * sc + be, dout + k, slope);
     if (u) g = u[k] >= p ? g * keep_scale : 0.f;
-    dy[k] = sc * (g - c1 - (x - m) * is * c2);
+    if constexpr (BATCH) dy[k] = sc * (g - c1 - (x - m) * is * c2);
+    else dy[k] = sc * g;
   }
 }
 
@@ -356,29 +363,32 @@ static int bn_act_dropout(const char* what, int B, int N, const float* y, const 
   if (B < 1 || N < 1) return fail(bad_arg, what, "B >= 1 and N >= 1 required");
   if (!y || !gamma || !beta || !out) return fail(bad_arg, what, "null pointer");
   if (LEAKY && !(slope >= 0.f && slope < 1.f)) return fail(bad_arg, what, "0 <= negative_slope < 1 required");
-  if (training) {
+  if (training != 0 && training != 1 && training != 2) return fail(bad_arg, what, "training must be 0, 1 or 2");
+  if (training == 1) {
     if (B < 2) return fail(bad_arg, what, "training-mode batch statistics need B >= 2");
     if (!mean || !invstd) return fail(bad_arg, what, "training mode writes mean and invstd");
     if (!(p >= 0.f && p < 1.f)) return fail(bad_arg, what, "0 <= p < 1 required");
-  } else {
+  } else {                                            // 0: eval; 2: a frozen BatchNorm under a live Dropout
     if (!running_mean || !running_var) return fail(bad_arg, what, "eval mode reads the running estimates");
-    u = nullptr;
+    if (training == 0) u = nullptr;
+    else if (!(p >= 0.f && p < 1.f)) return fail(bad_arg, what, "0 <= p < 1 required");
   }
   hipLaunchKernelGGL(bn_act_dropout_kernel<LEAKY>, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y, gamma,
-                     beta, eps, momentum, running_mean, running_var, num_batches_tracked, training, p, slope, u, out, mean,
-                     invstd);
+                     beta, eps, momentum, running_mean, running_var, num_batches_tracked, training == 1, p, slope, u, out,
+                     mean, invstd);
   return check_launch(what);
 }
 
-template <bool LEAKY>
+template <bool LEAKY, bool BATCH = true>
 static int bn_act_dropout_grad(const char* what, int B, int N, const float* y, const float* gamma, const float* beta,
                                const float* mean, const float* invstd, float slope, float p, const float* u,
                                const float* dout, float* dy, float* dgamma, float* dbeta, pdae_stream_t stream) {
-  if (B < 2 || N < 1) return fail(bad_arg, what, "B >= 2 and N >= 1 required");
+  if (BATCH && (B < 2 || N < 1)) return fail(bad_arg, what, "B >= 2 and N >= 1 required");
+  if (!BATCH && (B < 1 || N < 1)) return fail(bad_arg, what, "B >= 1 and N >= 1 required");
   if (LEAKY && !(slope >= 0.f && slope < 1.f)) return fail(bad_arg, what, "0 <= negative_slope < 1 required");
   if (!(p >= 0.f && p < 1.f)) return fail(bad_arg, what, "0 <= p < 1 required");
   if (!y || !gamma || !beta || !mean || !invstd || !dout || !dy || !dgamma || !dbeta) return fail(bad_arg, what, "null pointer");
-  hipLaunchKernelGGL(bn_act_dropout_grad_kernel<LEAKY>, dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y,
+  hipLaunchKernelGGL((bn_act_dropout_grad_kernel<LEAKY, BATCH>), dim3(blocks_for(N)), dim3(256), 0, as_stream(stream), B, N, y,
                      gamma, beta, mean, invstd, slope, p, u, dout, dy, dgamma, dbeta);
   return check_launch(what);
 }
@@ -398,6 +408,14 @@ extern "C" int pdae_bn_relu_dropout_grad(int B, int N, const float* y, const flo
                                     dgamma, dbeta, stream);
 }
 
+extern "C" int pdae_bn_relu_dropout_eval_grad(int B, int N, const float* y, const float* gamma, const float* beta,
+                                              const float* mean, const float* invstd, float p, const float* u,
+                                              const float* dout, float* dy, float* dgamma, float* dbeta,
+                                              pdae_stream_t stream) {
+  return bn_act_dropout_grad<false, false>("bn_relu_dropout_eval_grad", B, N, y, gamma, beta, mean, invstd, 0.f, p, u,
+                                           dout, dy, dgamma, dbeta, stream);
+}
+
 extern "C" int pdae_bn_lrelu_dropout(int B, int N, const float* y, const float* gamma, const float* beta, float eps,
                                      float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
                                      int training, float negative_slope, float p, const float* u, float* out, float* mean,
@@ -412,6 +430,14 @@ extern "C" int pdae_bn_lrelu_dropout_grad(int B, int N, const float* y, const fl
                                           pdae_stream_t stream) {
   return bn_act_dropout_grad<true>("bn_lrelu_dropout_grad", B, N, y, gamma, beta, mean, invstd, negative_slope, p, u,
                                    dout, dy, dgamma, dbeta, stream);
+}
+
+extern "C" int pdae_bn_lrelu_dropout_eval_grad(int B, int N, const float* y, const float* gamma, const float* beta,
+                                               const float* mean, const float* invstd, float negative_slope, float p,
+                                               const float* u, const float* dout, float* dy, float* dgamma,
+                                               float* dbeta, pdae_stream_t stream) {
+  return bn_act_dropout_grad<true, false>("bn_lrelu_dropout_eval_grad", B, N, y, gamma, beta, mean, invstd,
+                                          negative_slope, p, u, dout, dy, dgamma, dbeta, stream);
 }
 
 // the checks of the cross-entropy entries (have_ptrs: no null pointer among them); SMOOTH: one text for the shape and

@@ -29,6 +29,9 @@ LRELU_SLOPE = 0.2
 class DGCNN(Classifier):
     # parameters whose gradients backward produces last (FlatDataParallel lays them at the end of the flat buffer)
     late_grad_prefixes = ('dgcnn_encoder.',)
+    only_new_unsupported = ("set_bn_eval leaves dgcnn_encoder.bn4 (256 channels) in training mode beside frozen "
+                            "BatchNorms, and dgcnn_encoder's single autograd node differentiates training-mode "
+                            "BatchNorm only")
 
     def __init__(self, config, **kwargs):
         super().__init__()

@@ -70,15 +70,15 @@ def cls_max_concat(x):
 
 
 class _BnReluDropout(torch.autograd.Function):
-    """slope None: pdae_bn_relu_dropout (ReLU); a float: pdae_bn_lrelu_dropout (LeakyReLU with that negative slope)."""
+    """slope None: pdae_bn_relu_dropout (ReLU); a float: pdae_bn_lrelu_dropout (LeakyReLU with that negative slope).
+    training: 1 batch statistics (BatchNorm in training mode), 0 the running estimates and no dropout, 2 the running
+    estimates under a live Dropout (a frozen BatchNorm inside a model in training mode, runner_finetune.set_bn_eval)."""
 
     @staticmethod
     def forward(ctx, y, gamma, beta, bn, training, p, u, slope=None):
         B, N = y.shape
         out = empty((B, N), y)
-        mean = invstd = None
-        if training:
-            mean, invstd = empty((N,), y), empty((N,), y)
+        mean, invstd = empty((N,), y), empty((N,), y)      # batch statistics, or what the running estimates give
         track = bn.track_running_stats
         name, act = ('pdae_bn_relu_dropout', ()) if slope is None else ('pdae_bn_lrelu_dropout', (float(slope),))
         _lib.call(name, y, B, N, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), float(bn.eps),
@@ -93,20 +93,18 @@ class _BnReluDropout(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         what = 'bn_relu_dropout' if ctx.slope is None else 'bn_lrelu_dropout'
-        if not ctx.training:
-            raise NotImplementedError(what + ': the backward is implemented for training-mode BatchNorm')
         y, gamma, beta, mean, invstd, u = ctx.saved_tensors
         g = g.contiguous()
         B, N = y.shape
         dy, dgamma, dbeta = empty((B, N), g), empty((N,), g), empty((N,), g)
         act = () if ctx.slope is None else (float(ctx.slope),)
-        _lib.call('pdae_%s_grad' % what, g, B, N, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean),
-                  _lib.ptr(invstd), *act, float(ctx.p), _lib.ptr(u), _lib.ptr(g), _lib.ptr(dy), _lib.ptr(dgamma),
-                  _lib.ptr(dbeta))
+        name = 'pdae_%s_%s' % (what, 'grad' if ctx.training == 1 else 'eval_grad')
+        _lib.call(name, g, B, N, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(mean), _lib.ptr(invstd), *act,
+                  float(ctx.p), _lib.ptr(u), _lib.ptr(g), _lib.ptr(dy), _lib.ptr(dgamma), _lib.ptr(dbeta))
         return dy, dgamma, dbeta, None, None, None, None, None
 
 
-def _bn_act_dropout(what, y, bn, p, u, keep, slope):
+def _bn_act_dropout(what, y, bn, p, u, keep, slope, dropout=None):
     _gpu(y, what)
     if bn.momentum is None:
         raise NotImplementedError(what + ': cumulative moving average (momentum=None) is not supported')
@@ -118,25 +116,29 @@ def _bn_act_dropout(what, y, bn, p, u, keep, slope):
         u = _lib.require(u.contiguous(), 'u', dim=2)
         if tuple(u.shape) != tuple(y.shape):
             raise ValueError(f'{what}: the draw has shape {tuple(u.shape)}, the activation {tuple(y.shape)}')
-    if not bn.training or p == 0:
+    if dropout is None:
+        dropout = bn.training
+    if not dropout or p == 0:
         u = None
-    return _BnReluDropout.apply(_lib.require(y.contiguous(), 'y', dim=2), bn.weight, bn.bias, bn, bn.training, p, u,
-                                slope)
+    mode = 1 if bn.training else (2 if u is not None else 0)
+    return _BnReluDropout.apply(_lib.require(y.contiguous(), 'y', dim=2), bn.weight, bn.bias, bn, mode, p, u, slope)
 
 
-def bn_relu_dropout(y, bn, p, u=None, keep=None):
-    """Dropout(p)(ReLU(bn(y))) for y (B, N) and an nn.BatchNorm1d `bn` (its mode decides: training-mode batch statistics
-    and running-estimate updates, or the running estimates and no dropout).  The dropout draw is `u` (B, N uniforms: an
-    element is kept when u >= p) or `keep` (a boolean keep mask, injected by tests); neither = no dropout."""
-    return _bn_act_dropout('bn_relu_dropout', y, bn, p, u, keep, None)
+def bn_relu_dropout(y, bn, p, u=None, keep=None, dropout=None):
+    """Dropout(p)(ReLU(bn(y))) for y (B, N) and an nn.BatchNorm1d `bn`.  bn's mode decides the statistics: training-mode
+    batch statistics and running-estimate updates, or the running estimates (nothing written).  `dropout` decides
+    whether the draw applies -- the MODEL's training flag; None: bn's mode (a frozen BatchNorm inside a training-mode
+    model, runner_finetune.set_bn_eval, keeps its Dropout live).  The draw is `u` (B, N uniforms: an element is kept
+    when u >= p) or `keep` (a boolean keep mask, injected by tests); neither = no dropout."""
+    return _bn_act_dropout('bn_relu_dropout', y, bn, p, u, keep, None, dropout)
 
 
-def bn_lrelu_dropout(y, bn, p, slope, u=None, keep=None):
+def bn_lrelu_dropout(y, bn, p, slope, u=None, keep=None, dropout=None):
     """Dropout(p)(LeakyReLU(slope)(bn(y))), otherwise as bn_relu_dropout (the head of DGCNN, models/PointCAE_DGCNN.py:
     579-588; p = 0 for its first block, which has no Dropout).  0 <= slope < 1; slope 0 gives bn_relu_dropout's bits."""
     if not 0.0 <= float(slope) < 1.0:
         raise ValueError(f'bn_lrelu_dropout: 0 <= slope < 1 required, got {slope}')
-    return _bn_act_dropout('bn_lrelu_dropout', y, bn, p, u, keep, float(slope))
+    return _bn_act_dropout('bn_lrelu_dropout', y, bn, p, u, keep, float(slope), dropout)
 
 
 class _SoftmaxXent(torch.autograd.Function):

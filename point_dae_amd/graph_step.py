@@ -45,11 +45,12 @@ def _warn_if_null_stream():
 
 
 def _bn_buffers(module):
-    """running_mean / running_var / num_batches_tracked of every BatchNorm under `module`: the state a training-mode
-    forward changes besides the gradients."""
+    """running_mean / running_var / num_batches_tracked of every training-mode BatchNorm under `module`: the state a
+    forward changes besides the gradients.  A BatchNorm in eval mode (frozen by runner_finetune.set_bn_eval) is left
+    out: no forward writes its estimates, and nothing may write them back either."""
     out = []
     for m in module.modules():
-        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.running_mean is not None:
+        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.running_mean is not None and m.training:
             out += [m.running_mean, m.running_var, m.num_batches_tracked]
     return out
 

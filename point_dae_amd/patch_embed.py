@@ -291,18 +291,26 @@ def patch_embed_layerwise(points, first_conv, second_conv, groups=None):
     """Encoder.forward (models/PointCAE_transformer.py:37-51) layer by layer on the row GEMMs, calling the
     BatchNorm MODULES as they are -- which is what lets nn.SyncBatchNorm (collective C4 of SURVEY 2.2) compute its
     statistics across the replicas.  Slower than the fused path (every intermediate is materialised); used only under
-    --sync_bn.  The last conv + max-pool run on the listed groups only, like the fused path."""
+    --sync_bn and, from Encoder.forward, when a gradient is required through BatchNorms in eval mode (the frozen encoder
+    of optimizer.part only_new).  The last conv + max-pool run on the listed groups only, like the fused path."""
     BG, n, _ = points.shape
     R = BG * n
     y = linear_any(points.reshape(R, 3), first_conv[0].weight.squeeze(-1), first_conv[0].bias)
-    y = torch.relu(first_conv[1](y))
+    z1 = first_conv[1](y)
+    y = torch.relu(z1)
     f = linear_any(y, first_conv[3].weight.squeeze(-1), first_conv[3].bias)
     C2 = f.shape[1]
-    g = f.view(BG, n, C2).max(dim=1, keepdim=True)[0]
+    g, arg2 = f.view(BG, n, C2).max(dim=1, keepdim=True)
     cat = torch.cat([g.expand(-1, n, -1), f.view(BG, n, C2)], dim=2).reshape(R, 2 * C2)
     h = linear_any(cat, second_conv[0].weight.squeeze(-1), second_conv[0].bias)
-    h = torch.relu(second_conv[1](h))
+    z3 = second_conv[1](h)
+    h = torch.relu(z3)
     if groups is not None:
         h = h.view(BG, n, -1).index_select(0, groups.long()).reshape(-1, h.shape[1])
     t = linear_any(h, second_conv[3].weight.squeeze(-1), second_conv[3].bias)
-    return t.view(-1, n, t.shape[1]).max(dim=1)[0]
+    t, arg4 = t.view(-1, n, t.shape[1]).max(dim=1)
+    if DECISION_HOOK is not None:             # the BatchNorm outputs stand in for (rows, scale, shift): scale 1, shift 0
+        one, zero = (lambda c: torch.ones(c, device=t.device)), (lambda c: torch.zeros(c, device=t.device))
+        DECISION_HOOK(dict(y1=z1, sc1=one(z1.shape[1]), sh1=zero(z1.shape[1]), arg2=arg2.squeeze(1).to(torch.uint8),
+                           h3=z3, sc2=one(z3.shape[1]), sh2=zero(z3.shape[1]), arg4=arg4.to(torch.uint8)))
+    return t

@@ -25,7 +25,7 @@ from .arena import arena, begin_step
 from .chamfer_dist import ChamferDistanceL1, ChamferDistanceL2
 from .corrupt_util_tensor import corrupt_patches, draw_corruption
 from .knn_cuda import knn
-from .patch_embed import patch_embed
+from .patch_embed import patch_embed, patch_embed_layerwise
 from .pointnet2_utils import furthest_point_sample_with_centres
 from .registry import MODELS
 from .rows import linear_any, pad2d, split_weight_cols
@@ -66,7 +66,18 @@ class Encoder(nn.Module):
         """(B,G,n,3) -> tokens (B,G,C); with `groups` (int32 flat group ids) only their
         tokens, as rows (len(groups), C); `masked` = the complementary list."""
         bs, g, n, _ = point_groups.shape
-        tok = patch_embed(point_groups.reshape(bs * g, n, 3), self.first_conv, self.second_conv, self.training, groups, masked)
+        # the BatchNorm mode is the BatchNorm modules' own: the same as self.training unless a runner froze them
+        # (runner_finetune.set_bn_eval).  Then BatchNorms in eval mode under a required gradient, or two BatchNorms in
+        # different modes, take the layer-by-layer path: torch's BatchNorm modules differentiate in eval mode, the
+        # fused backward is written for batch statistics
+        bn_train = self.first_conv[1].training
+        mixed = self.second_conv[1].training != bn_train
+        frozen_grad = (bn_train != self.training and not bn_train and torch.is_grad_enabled()
+                       and any(p.requires_grad for p in self.parameters()))
+        if mixed or frozen_grad:
+            tok = patch_embed_layerwise(point_groups.reshape(bs * g, n, 3), self.first_conv, self.second_conv, groups)
+        else:
+            tok = patch_embed(point_groups.reshape(bs * g, n, 3), self.first_conv, self.second_conv, bn_train, groups, masked)
         return tok if groups is not None else tok.reshape(bs, g, self.encoder_channel)
 
 

@@ -1,4 +1,5 @@
-"""Classification fine-tuning model, MI355X host side (models/Point_MAE.py:578-706 PointTransformer of the reference).
+"""Classification fine-tuning models, MI355X host side (models/Point_MAE.py:578-706 PointTransformer and :846-966
+PointTransformerLinearClassification of the reference; the two differ in cls_head_finetune only).
 
 Same parameter names and shapes as the reference, so a pretraining checkpoint of this repository loads through
 builder.remap_pretrain_keys (the 'MAE_encoder.' prefix dropped) with strict=False, reporting the same missing and
@@ -26,8 +27,8 @@ from .registry import MODELS
 MAX_TOKENS = 128           # the attention kernels take T <= 128 tokens per cloud (csrc/attention.hip)
 
 
-@MODELS.register_module()
-class PointTransformer(Classifier):
+class _TransformerClassifier(Classifier):
+    """The trunk both classifiers share; a subclass gives build_head() -> cls_head_finetune."""
     # parameters whose gradients backward produces last (FlatDataParallel lays them at the end of the flat buffer)
     late_grad_prefixes = ('encoder.',)
 
@@ -44,10 +45,11 @@ class PointTransformer(Classifier):
         self.encoder_dims = config.encoder_dims
         if self.num_group + 1 > MAX_TOKENS:
             raise NotImplementedError(
-                'PointTransformer: num_group + 1 = %d tokens per cloud; the attention kernels take at most %d'
-                % (self.num_group + 1, MAX_TOKENS))
+                '%s: num_group + 1 = %d tokens per cloud; the attention kernels take at most %d'
+                % (type(self).__name__, self.num_group + 1, MAX_TOKENS))
         if self.encoder_dims != self.trans_dim:
-            raise NotImplementedError('PointTransformer: encoder_dims must equal trans_dim (the tokens feed the blocks)')
+            raise NotImplementedError('%s: encoder_dims must equal trans_dim (the tokens feed the blocks)'
+                                      % type(self).__name__)
         self.group_divider = Group(num_group=self.num_group, group_size=self.group_size)
         self.encoder = Encoder(encoder_channel=self.encoder_dims)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, self.trans_dim))
@@ -56,10 +58,7 @@ class PointTransformer(Classifier):
         dpr = [x.item() for x in torch.linspace(0, self.drop_path_rate, self.depth)]
         self.blocks = TransformerEncoder(self.trans_dim, self.depth, self.num_heads, dpr)
         self.norm = nn.LayerNorm(self.trans_dim)
-        self.cls_head_finetune = nn.Sequential(
-            nn.Linear(self.trans_dim * 2, 512), nn.BatchNorm1d(512), nn.ReLU(inplace=True), nn.Dropout(0.5),
-            nn.Linear(512, 256), nn.BatchNorm1d(256), nn.ReLU(inplace=True), nn.Dropout(0.5),
-            nn.Linear(256, self.cls_dim))
+        self.cls_head_finetune = self.build_head()
         trunc_normal_(self.cls_token, std=.02)
         trunc_normal_(self.cls_pos, std=.02)
 
@@ -79,3 +78,22 @@ class PointTransformer(Classifier):
         if capture is not None:
             capture.update(center=center, tokens=tokens, x=x, feature=f)
         return f
+
+
+@MODELS.register_module()
+class PointTransformer(_TransformerClassifier):
+    """Point_MAE.py:578-706: the MLP head (full fine-tuning, and the non-linear protocol on a frozen encoder)."""
+
+    def build_head(self):
+        return nn.Sequential(
+            nn.Linear(self.trans_dim * 2, 512), nn.BatchNorm1d(512), nn.ReLU(inplace=True), nn.Dropout(0.5),
+            nn.Linear(512, 256), nn.BatchNorm1d(256), nn.ReLU(inplace=True), nn.Dropout(0.5),
+            nn.Linear(256, self.cls_dim))
+
+
+@MODELS.register_module()
+class PointTransformerLinearClassification(_TransformerClassifier):
+    """Point_MAE.py:846-966: one Linear(2C, cls_dim) on the pooled feature (the linear protocol on a frozen encoder)."""
+
+    def build_head(self):
+        return nn.Sequential(nn.Linear(self.trans_dim * 2, self.cls_dim))

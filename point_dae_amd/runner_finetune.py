@@ -23,6 +23,22 @@ from .svm_probe import Acc_Metric
 POINT_ALL = {1024: 1200, 2048: 2400, 4096: 4800, 8192: 8192}      # runner_finetune.py:160-171
 
 
+def set_bn_eval(m):
+    """tools/runner_finetune.py:30-37, applied to every module after train() under optimizer.part only_new: a BatchNorm
+    whose width is not 256 belongs to the pretrained model and runs on its running estimates (256 is the new head's
+    BatchNorm, which keeps learning its own).  Dropout and DropPath stay live."""
+    if 'BatchNorm' in type(m).__name__ and m.weight.size(0) != 256:
+        m.eval()
+
+
+def set_train_mode(model, part):
+    """The mode of a training epoch: train(), then set_bn_eval under only_new (runner_finetune.py:141-146)."""
+    model.train()
+    if part == 'only_new':
+        model.apply(set_bn_eval)
+    return model
+
+
 def subset_indices(npoints, point_all):
     """The host draw of runner_finetune.py:174: npoints of the point_all FPS indices, without replacement."""
     return np.random.choice(point_all, npoints, False)
@@ -99,6 +115,10 @@ def run_net(args, config, log=print, log_every=20):
                           device, args.seed, rank, world, bs)
 
     base_model = builder.model_builder(config.model)
+    part = config.optimizer.get('part', 'all')
+    if part == 'only_new' and getattr(base_model, 'only_new_unsupported', None):
+        raise NotImplementedError('runner_finetune: optimizer.part only_new with %s: %s'
+                                  % (type(base_model).__name__, base_model.only_new_unsupported))
     start_epoch, best_metric = 0, 0.
     if args.resume:
         start_epoch, best_metric = builder.resume_model(base_model, args)
@@ -111,9 +131,9 @@ def run_net(args, config, log=print, log_every=20):
     optimizer, scheduler = builder.build_opti_sche(model, config)
     from .optim import FlatAdamW
     if not isinstance(optimizer, FlatAdamW):
-        raise NotImplementedError('runner_finetune: the fused AdamW (optimizer.part: all) is the only optimiser that '
-                                  'reads the device-side clip coefficient; part %r is not supported'
-                                  % config.optimizer.get('part', 'all'))
+        raise NotImplementedError('runner_finetune: the fused AdamW (optimizer.part: all, only_new, diff_lr) is the only '
+                                  'optimiser that reads the device-side clip coefficient; part %r is not supported'
+                                  % part)
     model.zero_grad()
     clip = GradNormClip(model.flat_grad, config.grad_norm_clip) if config.get('grad_norm_clip') is not None else None
     if int(config.get('step_per_update', 1)) != 1:
@@ -126,7 +146,9 @@ def run_net(args, config, log=print, log_every=20):
         log('step: hipGraph replay (GraphedClassifierStep)')
 
     for epoch in range(start_epoch, config.max_epoch + 1):
-        model.train()
+        # (the BatchNorm modes are the same every epoch, so the graph captured in the first one stays valid; the clip
+        # coefficient is taken over the WHOLE flat gradient under every part, as clip_grad_norm_(parameters()) is)
+        set_train_mode(model, part)
         if hasattr(train_loader, 'set_epoch'):
             train_loader.set_epoch(epoch)
         acc_sum = torch.zeros(2, device=device)

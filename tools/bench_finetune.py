@@ -13,7 +13,14 @@ JSON line:
                     head_loss_kernel_us its device kernels and their summed device time, kernel_us_per_step that sum
                     for the whole eager step
 
-    timeout -k 10 300 python tools/bench_finetune.py [--model DGCNN] [--steps 30 --warmup 10 --reps 50]
+  adamw_segments_all_us   (with --part) the ONE segmented launch over part all's two ranges, beside adamw_two_launch_us,
+                    the two launches it generalises, on scratch copies of the flat buffers, `--reps` calls each,
+                    three alternating rounds (min / max of the rounds: the run-to-run spread)
+
+--part only_new | diff_lr times the frozen-encoder protocols (optimizer.part; only_new runs in train() + set_bn_eval);
+--model PointTransformerLinearClassification is the linear protocol's model.
+
+    timeout -k 10 300 python tools/bench_finetune.py [--model DGCNN] [--part only_new] [--steps 30 --warmup 10 --reps 50]
 """
 import argparse
 import json
@@ -24,7 +31,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-CONFIGS = {'PointTransformer': 'finetune_modelnet_transferring_features.yaml', 'DGCNN': 'finetune_modelnet_dgcnn_smooth.yaml'}
+CONFIGS = {'PointTransformer': 'finetune_modelnet_transferring_features.yaml', 'DGCNN': 'finetune_modelnet_dgcnn_smooth.yaml',
+           'PointTransformerLinearClassification': 'finetune_modelnet_linear_classification.yaml'}
 
 
 def _kernels(fn):
@@ -60,6 +68,7 @@ def main(argv=None):
     p.add_argument('--reps', type=int, default=50)
     p.add_argument('--batch', type=int, default=32)
     p.add_argument('--model', choices=sorted(CONFIGS), default='PointTransformer')
+    p.add_argument('--part', choices=['all', 'only_new', 'diff_lr'], default=None, help='optimizer.part (default: the config\'s)')
     a = p.parse_args(argv)
     import torch
     from point_dae_amd import builder
@@ -67,10 +76,13 @@ def main(argv=None):
     from point_dae_amd.data_parallel import FlatDataParallel
     from point_dae_amd.finetune_ops import GradNormClip
     from point_dae_amd.graph_step import GraphedClassifierStep, use_created_stream
-    from point_dae_amd.runner_finetune import resample, train_step
+    from point_dae_amd.runner_finetune import resample, set_train_mode, train_step
     from point_dae_amd.synthetic import labelled_clouds
 
     config = cfg_from_yaml_file(os.path.join(ROOT, 'cfgs', CONFIGS[a.model]))
+    if a.part is not None:
+        config.optimizer.part = a.part
+    part = config.optimizer.get('part', 'all')
     B, N = a.batch, config.npoints
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
@@ -78,16 +90,16 @@ def main(argv=None):
     x, y = labelled_clouds(B, 2048, seed=0, classes=3)
     pts = resample(torch.from_numpy(x).to(dev), N)
     labels = torch.from_numpy(y).to(dev)
-    if a.model == 'PointTransformer':
-        out = dict(workload='finetune_modelnet', batch=B, npoints=N, num_group=config.model.num_group,
+    if a.model != 'DGCNN':
+        out = dict(workload='finetune_modelnet', model=a.model, part=part, batch=B, npoints=N, num_group=config.model.num_group,
                    tokens=config.model.num_group + 1, depth=config.model.depth, steps=a.steps, warmup=a.warmup)
     else:
-        out = dict(workload='finetune_modelnet_dgcnn', batch=B, npoints=N, smoothloss=bool(config.model.smoothloss),
+        out = dict(workload='finetune_modelnet_dgcnn', part=part, batch=B, npoints=N, smoothloss=bool(config.model.smoothloss),
                    steps=a.steps, warmup=a.warmup)
 
     def setup():
         torch.manual_seed(0)
-        net = builder.model_builder(config.model).to(dev).train()
+        net = set_train_mode(builder.model_builder(config.model).to(dev), part)
         model = FlatDataParallel(net)
         opt, _ = builder.build_opti_sche(model, config)
         model.zero_grad()
@@ -130,6 +142,28 @@ def main(argv=None):
     out['grad_norm_clip_us'] = round(_events_ms(clip, a.reps) * 1e3, 2)
     out['grad_norm_clip_GBps'] = round(4.0 * model.flat_grad.numel() / (out['grad_norm_clip_us'] * 1e-6) / 1e9, 1)
     out['adamw_step_gscale_us'] = round(_events_ms(lambda: opt.step(grad_scale=coef), a.reps) * 1e3, 2)
+    if a.part is not None:
+        from point_dae_amd import _lib
+        m = model
+        bufs = [m.flat_param.clone(), m.flat_grad.clone(), torch.zeros_like(m.flat_param), torch.zeros_like(m.flat_param)]
+        kw = config.optimizer.kwargs
+        lr = float(kw.lr)
+        ranges = [m.no_decay_range + (0.0,), m.decay_range + (float(kw.weight_decay),)]
+
+        def two():
+            for lo, hi, wd in ranges:
+                _lib.call('pdae_adamw_step_gscale', bufs[0], hi - lo, *[t[lo:].data_ptr() for t in bufs], lr, 0.9, 0.999,
+                          1e-8, wd, 1, coef.data_ptr())
+
+        def one():
+            _lib.adamw_step_segments(*bufs, [(lo, hi - lo, lr, wd) for lo, hi, wd in ranges], 0.9, 0.999, 1e-8, 1, coef)
+        two(), one()
+        rounds = [(_events_ms(two, a.reps) * 1e3, _events_ms(one, a.reps) * 1e3) for _ in range(3)]
+        out['adamw_two_launch_us'] = [round(min(r[0] for r in rounds), 2), round(max(r[0] for r in rounds), 2)]
+        out['adamw_segments_all_us'] = [round(min(r[1] for r in rounds), 2), round(max(r[1] for r in rounds), 2)]
+        out['adamw_launches_per_step'] = 2 if part == 'all' else -(-sum(len(g['segments']) for g in opt.param_groups) // 8)
+        if part != 'all':
+            out['adamw_segments'] = sum(len(g['segments']) for g in opt.param_groups)
     out['device'] = torch.cuda.get_device_name(dev)
     print(json.dumps(out))
 
