@@ -115,6 +115,17 @@ int pdae_gather_points(int b, int c, int n, int npoints, const float* points,
 int pdae_gather_points_grad(int b, int c, int n, int npoints,
                             const float* grad_out, const int32_t* idx,
                             float* grad_points, pdae_stream_t stream);
+/* The fine-tuning runner's batch preparation behind FPS in one launch (tools/runner_finetune.py:415-420: the host's
+ * subset of the FPS order, the gather, train_transforms) with the per-cloud map of datasets/data_transforms.py
+ * (PointcloudRotate: A, PointcloudScaleAndTranslate: diagonal A and t):
+ *   out[b,n,j] = sum_i raw[b, fps_idx[b, choice[n]], i] * A[b,i,j] + t[b,j]        i, j in 0..2
+ * raw (b,p,c) with c >= 3 (only the first three channels are read), fps_idx (b,point_all), choice (npoints) shared by
+ * the batch, A (b,3,3) and t (b,3) each nullable, out (b,npoints,3).  A == t == NULL moves the coordinates bit for bit;
+ * with a map the sum runs i = 0, 1, 2, then + t, every operation rounded.  An index outside its array is not followed
+ * (that point is written as NaN).  c < 3, npoints > point_all and non-positive sizes: PDAE_ERR_BAD_ARG.            */
+int pdae_resample_affine(int b, int p, int c, int point_all, int npoints, const float* raw, const int32_t* fps_idx,
+                         const int32_t* choice, const float* A /*nullable*/, const float* t /*nullable*/, float* out,
+                         pdae_stream_t stream);
 
 /* query_ball_point_kernel_wrapper(b, n, m, radius, nsample, new_xyz, xyz, idx)
  *   ball_query_gpu.cu:49-57 (kernel :12-47), host ball_query.cpp:11-35.

@@ -21,6 +21,7 @@ _SIGNATURES = {
     "pdae_furthest_point_sampling": [_i, _i, _i, _vp, _vp, _vp, _vp],
     "pdae_gather_points": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "pdae_gather_points_grad": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "pdae_resample_affine": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_ball_query": [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
     "pdae_group_points": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "pdae_group_points_grad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],

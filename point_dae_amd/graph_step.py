@@ -561,3 +561,14 @@ class GraphedClassifierStep(_OneGraphStep):
             coef = self.clip() if self.clip is not None else None
         self.optimizer.step(grad_scale=coef)
         return loss, acc
+
+    def step_filled(self, labels):
+        """__call__ for a batch that is already in self.points: the caller's own launch wrote it there, on the current
+        stream (data_transforms.resample_transformed(..., out=self.points)), so there is nothing to copy."""
+        self.labels.copy_(labels, non_blocking=True)
+        loss, acc, coef = self._run()
+        if self.model.world_size > 1:
+            _average_gradients(self.model)
+            coef = self.clip() if self.clip is not None else None
+        self.optimizer.step(grad_scale=coef)
+        return loss, acc

@@ -1,6 +1,6 @@
 """Entry point: `python -m point_dae_amd.main --config cfgs/X.yaml [--launcher pytorch]`
 (main.py:16-111 of the reference): pretraining, or with --finetune_model / --scratch_model the
-classification fine-tuning runner."""
+classification fine-tuning runner (--so3_rotation: its rotation-robustness protocol)."""
 import torch
 
 from . import dist_utils, parser
@@ -36,7 +36,9 @@ def main(argv=None):
     assert config.total_bs % args.world_size == 0
     config.dataset.train.others.bs = config.total_bs // args.world_size
     set_random_seed(args.seed + args.local_rank, deterministic=args.deterministic)   # main.py:78-81
-    if finetune:
+    if finetune and args.so3_rotation:
+        runner_finetune.run_net_rotation(args, config)                     # main.py:106-107
+    elif finetune:
         runner_finetune.run_net(args, config)                              # main.py:96-103
     else:
         runner_pretrain.run_net(args, config)

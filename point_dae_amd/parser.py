@@ -24,6 +24,8 @@ def get_args(argv=None):
     p.add_argument('--total_bs', type=int, default=-1)
     p.add_argument('--finetune_model', action='store_true', default=False, help='finetune modelnet with pretrained weight')
     p.add_argument('--scratch_model', action='store_true', default=False, help='training modelnet from scratch')
+    p.add_argument('--so3_rotation', action='store_true', default=False,
+                   help='rotation-robustness fine-tuning: y-axis train rotation, ten-pass rotated validation')
     # synthetic-data controls (no dataset ships with this repo)
     p.add_argument('--max_epoch', type=int, default=-1, help='override config.max_epoch')
     p.add_argument('--steps_per_epoch', type=int, default=None,

@@ -5,6 +5,9 @@ forward, cross-entropy, backward; the gradient-norm clip (clip_grad_norm_ with `
 epoch-granular CosLR; validation on the test set with FPS to `npoints`, argmax accuracy, ckpt-best / ckpt-last.  The
 clip coefficient stays on the device (finetune_ops.GradNormClip -> FlatAdamW grad_scale), and loss / accuracy are
 accumulated on the device and read back once per log line, where the reference calls .item() twice per step.
+
+run_net_rotation / validate_rotation (:322-564, main.py --so3_rotation) are the same loop with a train transform inside
+the resample (data_transforms.resample_transformed: one launch into the graphed step's input) and ten validation passes.
 """
 import time
 
@@ -73,10 +76,9 @@ def train_step(model, optimizer, clip, points, labels):
     return loss.detach(), acc.detach()
 
 
-@torch.no_grad()
-def validate(base_model, test_loader, epoch, config, args=None, log=print):
-    """runner_finetune.py:273-318: FPS to npoints, eval forward, argmax accuracy over the whole test set."""
-    base_model.eval()
+def _predict(base_model, test_loader, config, args=None):
+    """One pass over the test loader: FPS to npoints, eval forward, argmax -> (pred, label) of every test cloud [of every
+    rank]."""
     preds, labels = [], []
     for _, _, data in test_loader:
         points, label = data[0].cuda(), data[1].cuda()
@@ -86,9 +88,31 @@ def validate(base_model, test_loader, epoch, config, args=None, log=print):
     pred, label = torch.cat(preds), torch.cat(labels)
     if args is not None and getattr(args, 'distributed', False):
         pred, label = dist_utils.gather_tensor(pred, args), dist_utils.gather_tensor(label, args)
+    return pred, label
+
+
+@torch.no_grad()
+def validate(base_model, test_loader, epoch, config, args=None, log=print):
+    """runner_finetune.py:273-318: FPS to npoints, eval forward, argmax accuracy over the whole test set."""
+    base_model.eval()
+    pred, label = _predict(base_model, test_loader, config, args)
     acc = float((pred == label).sum().item()) / float(label.numel()) * 100.
     log('[Validation] EPOCH: %d  acc = %.4f' % (epoch, acc))
     return Acc_Metric(acc)
+
+
+@torch.no_grad()
+def validate_rotation(base_model, test_loader, epoch, config, args=None, log=print, passes=10):
+    """runner_finetune.py:515-564: `passes` full passes over the test loader, whose 'rotate' / 'rotate_z' item draws a fresh
+    rotation for every cloud on every pass; the accuracy of each pass (gathered per pass), then their fp32 mean."""
+    base_model.eval()
+    accs = []
+    for _ in range(passes):
+        pred, label = _predict(base_model, test_loader, config, args)
+        accs.append((pred == label).sum() / float(label.size(0)) * 100.)
+    acc = torch.Tensor([float(a) for a in accs]).mean()
+    log('[Validation] EPOCH: %d  acc = %.4f' % (epoch, acc))
+    return Acc_Metric(float(acc))
 
 
 def _loader(node, device, seed, rank, world, bs, steps_per_epoch=None):
@@ -104,6 +128,19 @@ def _loader(node, device, seed, rank, world, bs, steps_per_epoch=None):
 
 
 def run_net(args, config, log=print, log_every=20):
+    return _run(args, config, log, log_every)
+
+
+def run_net_rotation(args, config, log=print, log_every=20):
+    """runner_finetune.py:322-511 (--so3_rotation; z/z, z/SO(3) and SO(3)/SO(3) alike): run_net with train_transforms --
+    data_transforms.PointcloudRotate, a y-axis rotation per cloud -- behind the resample, and validate_rotation."""
+    from .data_transforms import PointcloudRotate
+    return _run(args, config, log, log_every, train_transform=PointcloudRotate(), validate_fn=validate_rotation)
+
+
+def _run(args, config, log, log_every, train_transform=None, validate_fn=validate):
+    """The loop of run_net.  With a train_transform the batch is prepared by data_transforms.resample_transformed (the
+    subset, the gather and the transform's map: one launch, straight into the graphed step's input buffer)."""
     rank, world = dist_utils.get_dist_info()
     device = torch.device('cuda', torch.cuda.current_device())
     from .graph_step import use_created_stream
@@ -141,9 +178,13 @@ def run_net(args, config, log=print, log_every=20):
     best_metrics, metrics = Acc_Metric(best_metric), Acc_Metric(0.)
     # the step is replayed as a hipGraph (graph_step.GraphedClassifierStep)
     from .graph_step import GraphedClassifierStep
+    if train_transform is not None:
+        from .data_transforms import resample_transformed
     graphed = GraphedClassifierStep(model, optimizer, clip, bs, config.npoints)
     if rank == 0:
         log('step: hipGraph replay (GraphedClassifierStep)')
+        if train_transform is not None:
+            log('train transform: %s inside the resample; validation: %s' % (type(train_transform).__name__, validate_fn.__name__))
 
     for epoch in range(start_epoch, config.max_epoch + 1):
         # (the BatchNorm modes are the same every epoch, so the graph captured in the first one stays valid; the clip
@@ -154,8 +195,12 @@ def run_net(args, config, log=print, log_every=20):
         acc_sum = torch.zeros(2, device=device)
         t0, n = time.time(), 0
         for idx, (_, _, data) in enumerate(train_loader):
-            points = resample(data[0], config.npoints)
-            loss, acc = graphed(points, data[1])                 # (the train loader yields only full batches)
+            if train_transform is None:
+                points = resample(data[0], config.npoints)
+                loss, acc = graphed(points, data[1])             # (the train loader yields only full batches)
+            else:
+                resample_transformed(data[0], config.npoints, train_transform, out=graphed.points)
+                loss, acc = graphed.step_filled(data[1])
             acc_sum += torch.stack([loss, acc])
             n += 1
             if (idx + 1) % log_every == 0 or idx + 1 == len(train_loader):
@@ -171,7 +216,7 @@ def run_net(args, config, log=print, log_every=20):
             if item is not None:
                 item.step(epoch)
         if epoch % max(int(getattr(args, 'val_freq', 1)), 1) == 0:
-            metrics = validate(base_model, test_loader, epoch, config, args, log=log)
+            metrics = validate_fn(base_model, test_loader, epoch, config, args, log=log)
             if metrics.better_than(best_metrics):
                 best_metrics = metrics
                 builder.save_checkpoint(model, optimizer, epoch, metrics, best_metrics, 'ckpt-best', args)
