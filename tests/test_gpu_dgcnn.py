@@ -3,7 +3,9 @@ formulation written with framework ops in fp32 (models/dgcnn_util.py:7-34 knn / 
 Conv2d -> BatchNorm2d -> LeakyReLU(0.2) -> max over the 20 neighbours of every EdgeConv, conv5's BatchNorm1d ->
 LeakyReLU -> max over the points).  Indices bit-exact (the selection is exact on the reference's expression); floating
 point 2e-5 relative on activations, 1e-3 relative L2 on gradients (typically 1e-5; tolerances and their reasons in the tests).
-The model-level fixture of the live reference is tests/test_gpu_model.py::test_dgcnn_product_model_reproduces_reference_fixture."""
+The model-level fixture of the live reference is tests/test_gpu_model.py::test_dgcnn_product_model_reproduces_reference_fixture.
+Kernel-level coverage -- every EdgeConv / cloud-pool entry point on its own against fp64, elementwise, at all accepted
+widths, on hub graphs, with exact ties and 16-bit-wide winner ids -- is tests/test_gpu_dgcnn_kernels.py."""
 import numpy as np
 import pytest
 import torch
