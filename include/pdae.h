@@ -1047,6 +1047,39 @@ int pdae_grad_norm_clip(long long n, const float* grad, float max_norm, double* 
                         float* coef, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Linear-SVM evaluation protocol (csrc/svm.hip; tools/runner_finetune.py:1038-1049 of the reference fits
+ * sklearn.svm.SVC(C=c, kernel='linear'), i.e. libsvm's one-vs-one C-SVC, for six values of C).
+ * The n training samples are ordered by class: order[s] (device, n ints) is the Gram row of the s-th sample in class
+ * order, class_ptr (HOST, K + 1 ints, 0 .. n, every class non-empty) the classes' ranges in it.  Cs: HOST, nC doubles.
+ * Pairs (p, q), p < q, are numbered (0,1), (0,2), ..., P = K (K - 1) / 2.
+ *   svm_ovo_train    the dual C-SVC of every (pair, C), one workgroup each, from the training Gram matrix G = X X^T
+ *                    (n x ld fp32, ld >= n): SMO on the maximal violating pair, alpha and gradient in fp64, stopped
+ *                    when the violation is < eps (libsvm's -e; the protocol's is 1e-3) or after max_iter iterations.
+ *                    Ties go to the lowest member: two runs give the same bits.
+ *                    coef (nC, K - 1, n) fp64 = alpha_s y_s in libsvm's dual_coef_ rows with the columns in class
+ *                    order: the s-th sample, of class p, against class q sits in row q - 1 if q > p, else in row q.
+ *                    rho (nC, P) by libsvm's calculate_rho; status (nC, P, 2) = iterations, 1 when max_iter was hit;
+ *                    gap (nC, P) the final violation.  All outputs are fully written.
+ *                    A pair of more than PDAE_SVM_MAX_PAIR members, K > PDAE_SVM_MAX_CLASSES: PDAE_ERR_UNSUPPORTED,
+ *                    nothing is launched.  max_iter < 1, nC outside 1 .. PDAE_SVM_MAX_C, C <= 0: PDAE_ERR_BAD_ARG.
+ *   svm_ovo_predict  from the test-by-train Gram matrix Gte (m x ld fp32): dec (nC, m, P) fp64 = sum over the pair's
+ *                    members of coef * Gte - rho (lane-strided partial sums added in a fixed order), pred (nC, m)
+ *                    int32 = libsvm's vote as a class INDEX 0 .. K - 1: dec > 0 votes for the pair's first class,
+ *                    else for its second; the first class with the most votes.  n <= PDAE_SVM_PREDICT_MAX_TRAIN.   */
+#define PDAE_SVM_MAX_PAIR 2048
+#define PDAE_SVM_MAX_CLASSES 64
+#define PDAE_SVM_MAX_C 8
+#define PDAE_SVM_PREDICT_MAX_TRAIN 12288
+int pdae_svm_ovo_train(int n, int ld, int K, int nC, const float* G, const int* order, const int* class_ptr /*host*/,
+                       const double* Cs /*host*/, double eps, int max_iter, double* coef, double* rho, int* status,
+                       double* gap, pdae_stream_t stream);
+/* host-side: the status svm_ovo_train would refuse this layout with (no stream, nothing launched) */
+int pdae_svm_ovo_supported(int n, int K, int nC, const int* class_ptr /*host*/, const double* Cs /*host*/, int max_iter);
+int pdae_svm_ovo_predict(int m, int n, int ld, int K, int nC, const float* Gte, const int* order,
+                         const int* class_ptr /*host*/, const double* coef, const double* rho, double* dec, int* pred,
+                         pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Measurement aids: box calibration for bench.py (csrc/calib.hip).  They replace nothing of the reference; the training
  * step never calls them.  MI355X boxes differ by +-4 % on the step and by up to 12 % on matrix loops (the clock a device
  * holds under load), so a bench line carries the rates of two kernels of known work next to its headline.

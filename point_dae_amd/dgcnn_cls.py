@@ -14,9 +14,13 @@ The encoder is the auto-encoder's explicit kernel sequence (csrc/dgcnn.hip).  Th
 Linear layers on the row GEMMs (rows.linear_any) and each BatchNorm + LeakyReLU [+ Dropout] as one launch
 (finetune_ops.bn_lrelu_dropout); the loss is finetune_ops.softmax_xent_smooth (smoothloss) or softmax_xent.  There is
 no CPU path.
+
+DGCNN_feat (models/PointCAE_DGCNN.py:755-846) is the same encoder without the head: forward returns the (B, 1024) feature
+the linear-SVM evaluation protocol fits its classifiers on (runner_finetune.svm_classification).
 """
 import torch.nn as nn
 
+from .arena import begin_step
 from .classifier import Classifier
 from .point_cae_dgcnn import dgcnn_encoder
 from .registry import MODELS
@@ -58,3 +62,21 @@ class DGCNN(Classifier):
         if capture is not None:
             capture.update(feature=f)
         return f
+
+
+@MODELS.register_module()
+class DGCNN_feat(DGCNN):
+    """The frozen feature extractor of --svm_classification: dgcnn_encoder and nothing else that carries parameters, so a
+    Point_CAE_DGCNN_FCOnly checkpoint loads with recfc.* unexpected and nothing missing.  get_loss_acc,
+    load_model_from_ckpt and _init_weights are the classifier's (the reference's class carries the same copies)."""
+
+    def __init__(self, config, **kwargs):
+        super().__init__(config, **kwargs)
+        del self.cls_head_finetune
+
+    def forward(self, pts, capture=None):
+        """pts (B, N, 3+) -> the encoder's feature (B, 1024)."""
+        if not pts.is_cuda:
+            raise RuntimeError('DGCNN_feat: points must be on the GPU (there is no CPU path)')
+        begin_step(pts.device)
+        return self.trunk(pts[:, :, :3].contiguous(), capture)

@@ -1,6 +1,7 @@
 """Entry point: `python -m point_dae_amd.main --config cfgs/X.yaml [--launcher pytorch]`
 (main.py:16-111 of the reference): pretraining, or with --finetune_model / --scratch_model the
-classification fine-tuning runner (--so3_rotation: its rotation-robustness protocol)."""
+classification fine-tuning runner (--so3_rotation: its rotation-robustness protocol; --svm_classification: the linear-SVM
+evaluation of the frozen encoder)."""
 import torch
 
 from . import dist_utils, parser
@@ -14,6 +15,10 @@ def main(argv=None):
     args.use_gpu = torch.cuda.is_available()
     if not args.use_gpu:
         raise RuntimeError('point_dae_amd needs an MI355X: there is no CPU path')
+    if args.svm_classification and args.launcher != 'none':
+        # the reference runs this protocol in ONE process under DataParallel (rerun.sh); its distributed branch would fit
+        # every rank's SVMs on that rank's shard of the features
+        raise ValueError('--svm_classification runs in one process: --launcher none')
     if args.launcher == 'none':
         args.distributed = False
         args.world_size = 1
@@ -36,7 +41,9 @@ def main(argv=None):
     assert config.total_bs % args.world_size == 0
     config.dataset.train.others.bs = config.total_bs // args.world_size
     set_random_seed(args.seed + args.local_rank, deterministic=args.deterministic)   # main.py:78-81
-    if finetune and args.so3_rotation:
+    if finetune and args.svm_classification:
+        runner_finetune.svm_classification(args, config)                   # main.py:102-103
+    elif finetune and args.so3_rotation:
         runner_finetune.run_net_rotation(args, config)                     # main.py:106-107
     elif finetune:
         runner_finetune.run_net(args, config)                              # main.py:96-103

@@ -8,6 +8,9 @@ accumulated on the device and read back once per log line, where the reference c
 
 run_net_rotation / validate_rotation (:322-564, main.py --so3_rotation) are the same loop with a train transform inside
 the resample (data_transforms.resample_transformed: one launch into the graphed step's input) and ten validation passes.
+
+svm_classification (:902-1049, main.py --svm_classification) trains nothing: one eval pass of the frozen encoder over the
+train and the val loader, then the six linear SVMs of svm_ops on the features, which never leave the device.
 """
 import time
 
@@ -47,12 +50,13 @@ def subset_indices(npoints, point_all):
     return np.random.choice(point_all, npoints, False)
 
 
-def resample(points, npoints, choice=None):
-    """FPS of each cloud to point_all points, then the columns `choice` (default: a fresh host draw) of the FPS
-    order, gathered -> (B, npoints, 3) (runner_finetune.py:158-176)."""
+def resample(points, npoints, choice=None, point_all=None):
+    """FPS of each cloud to point_all points (default: the fine-tuning loop's oversampling POINT_ALL[npoints]), then the
+    columns `choice` (default: a fresh host draw) of the FPS order, gathered -> (B, npoints, 3)
+    (runner_finetune.py:158-176)."""
     if npoints not in POINT_ALL:
         raise NotImplementedError('npoints %d' % npoints)
-    point_all = min(POINT_ALL[npoints], points.shape[1])
+    point_all = min(POINT_ALL[npoints] if point_all is None else point_all, points.shape[1])
     xyz = points[:, :, :3].contiguous()
     fps_idx = furthest_point_sample(xyz, point_all)
     if choice is None:
@@ -222,3 +226,52 @@ def _run(args, config, log, log_every, train_transform=None, validate_fn=validat
                 builder.save_checkpoint(model, optimizer, epoch, metrics, best_metrics, 'ckpt-best', args)
         builder.save_checkpoint(model, optimizer, epoch, metrics, best_metrics, 'ckpt-last', args)
     return model
+
+
+@torch.no_grad()
+def extract_svm_features(base_model, loader, npoints):
+    """runner_finetune.py:955-987 / :1000-1031: per batch FPS to point_all = min(npoints, N) points -- no oversampling in
+    this protocol --, the host draw np.random.choice(point_all, npoints, False) (a permutation of the FPS order), the
+    gather, the eval forward -> (features (n, C), labels (n,)) on the device."""
+    feats, labels = [], []
+    for _, _, data in loader:
+        points = resample(data[0].cuda(), npoints, point_all=npoints)
+        feats.append(base_model(points).detach())
+        labels.append(data[1].cuda().view(-1))
+    return torch.cat(feats, 0), torch.cat(labels, 0)
+
+
+def svm_classification(args, config, log=print):
+    """runner_finetune.py:902-1049: the features of the train loader (its short last batch dropped), then of the val
+    loader, from the frozen model in eval mode; SVC(C=c, kernel='linear') for c = 10**i, i in range(-3, 3) (svm_ops:
+    the gfx950 solver, or PDAE_SVM=sklearn); the reference's lines -- the running best per c, then its
+    '[Validation] EPOCH' line, whose epoch field is the last c -- -> Acc_Metric(best test accuracy, a fraction)."""
+    from . import svm_ops
+    rank, world = dist_utils.get_dist_info()
+    device = torch.device('cuda', torch.cuda.current_device())
+    from .graph_step import use_created_stream
+    use_created_stream(device)
+    bs = config.total_bs // world
+    train_loader = _loader(config.dataset.train, device, args.seed + rank, rank, world, bs,
+                           getattr(args, 'steps_per_epoch', None))
+    test_loader = _loader(config.dataset.val, device, args.seed, rank, world, bs)
+    base_model = builder.model_builder(config.model)
+    if getattr(args, 'resume', False):
+        builder.resume_model(base_model, args)
+    elif args.ckpts is not None:
+        base_model.load_model_from_ckpt(args.ckpts, log=log)               # runner_finetune.py:921-922
+    else:
+        log('Training from scratch')                                       # (:924: the model keeps its constructor's init)
+    base_model = base_model.to(device).eval()
+    feats_train, labels_train = extract_svm_features(base_model, train_loader, config.npoints)
+    log(str(tuple(feats_train.shape)))
+    feats_test, labels_test = extract_svm_features(base_model, test_loader, config.npoints)
+    log(str(tuple(feats_test.shape)))
+    log('SVM backend: %s' % svm_ops.backend())
+    max_acc, c = 0, None
+    for c, acc in zip(svm_ops.SVM_CS, svm_ops.accuracies(feats_train, labels_train, feats_test, labels_test)):
+        if max_acc < acc:
+            max_acc = acc
+        log('%s %s' % (c, max_acc))
+    log('[Validation] EPOCH: %d  acc = %.4f' % (c, max_acc))
+    return Acc_Metric(max_acc)

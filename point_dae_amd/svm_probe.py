@@ -33,6 +33,19 @@ def evaluate_svm(train_features, train_labels, test_features, test_labels):
     return float(np.sum(test_labels == pred)) / pred.shape[0]
 
 
+def svc_accuracies(train_features, train_labels, test_features, test_labels, Cs):
+    """The reference's own classifier of --svm_classification on host features (tools/runner_finetune.py:1038-1047):
+    SVC(C=c, kernel='linear').fit(train).score(test) per c -> fractions.  Selected by PDAE_SVM=sklearn (svm_ops.accuracies);
+    the comparator of the gfx950 solver's tests."""
+    from sklearn.svm import SVC
+    accs = []
+    for c in Cs:
+        model_tl = SVC(C=c, kernel='linear')
+        model_tl.fit(train_features, train_labels)
+        accs.append(float(model_tl.score(test_features, test_labels)))
+    return accs
+
+
 @torch.no_grad()
 def extract_features(base_model, loader, npoints):
     """-> (features (n, C), labels (n,)) on the device; loader items: (taxonomy, model_id, (points, label))."""
