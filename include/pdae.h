@@ -84,9 +84,7 @@ int pdae_deterministic(void);   /* 1 when a workspace is registered */
 int pdae_deferred_begin(void* workspace, size_t bytes);
 int pdae_deferred_flush(pdae_stream_t stream);
 /* rows_wgrad parks its partial-tile reduction in the same window (the dW / db outputs and the workspace of the call
- * must then stay untouched until the flush, which adds the tiles of up to 8 parked launches per reduction launch).
- * deferred_hold(1) ... deferred_hold(0) brackets calls whose results the caller reads right away. */
-int pdae_deferred_hold(int hold);
+ * must then stay untouched until the flush, which adds the tiles of up to 8 parked launches per reduction launch). */
 
 /* ------------------------------------------------------------------------
  * Farthest point sampling.
@@ -406,29 +404,9 @@ int pdae_cloud_pool_backward(int b, int n, int C, const float* y, const float* g
                              float* dy, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
- * Dense layers.  The reference runs nn.Linear / 1x1 nn.Conv1d through
- * cuBLAS / cuDNN in fp32 (patch embedder models/PointCAE_transformer.py:24-51,
- * qkv / proj :113-137, fc1 / fc2 :94-110, pos_embed :329-333, increase_dim
- * :653-658).  Here: fp32-input MFMA (exact fp32 accumulation), row-major
- * activations (rows, channels), weights in torch's (out, in) layout.
- *   forward:          Y[M,N]  = act(X[M,K] . W[N,K]^T + bias[N]); act 0 none,
- *                     1 ReLU, 2 GELU(erf); bias nullable; K % 4 == 0.
- *   backward_data:    dX[M,K] = dY[M,N] . W[N,K], given Wt = W^T as [K,N].
- *   backward_weight:  dW[N,K] = dY^T . X, dbias[N] = column sums of dY
- *                     (nullable); both are overwritten (zero-filled, then
- *                     accumulated with fp32 atomics over M-splits).
- */
-int pdae_linear_forward(int M, int N, int K, const float* X, const float* W,
-                        const float* bias /*nullable*/, int act, float* Y,
-                        pdae_stream_t stream);
-int pdae_linear_backward_data(int M, int N, int K, const float* dY,
-                              const float* Wt, float* dX, pdae_stream_t stream);
-int pdae_linear_backward_weight(int M, int N, int K, const float* dY,
-                                const float* X, float* dW,
-                                float* dbias /*nullable*/, pdae_stream_t stream);
-
-/* ------------------------------------------------------------------------
- * Dense layers of the Transformer blocks (csrc/rows_gemm.hip): Attention.qkv /
+ * Dense layers (csrc/rows_gemm.hip).  The reference runs nn.Linear / 1x1
+ * nn.Conv1d through cuBLAS / cuDNN in fp32; here: row-major activations
+ * (rows, channels), weights in torch's (out, in) layout, K % 4 == 0.  Attention.qkv /
  * proj (models/PointCAE_transformer.py:113-137), Mlp.fc1 / act / fc2 (:94-110),
  * pos_embed (:329-333), increase_dim (:653-658), and their backward.  Small-M
  * GEMMs (M = B * T tokens): a family of tile shapes, a per-shape plan, optional
@@ -479,27 +457,21 @@ int pdae_rows_gemm(int M, int N, int K, const float* X, const float* W, int w_kn
  * models/PointCAE_transformer.py:37-51, behind MaskTransformer.forward :424-469 which drops the masked tokens).
  * Rows of a group whose token is dropped carry no activation gradient into BatchNorm-2's backward, so their
  * conv-output gradient is the correction alone, dh = u + v * h (u, v per channel).  Entries:
- *   bnrelu_backward_listed: S (the sums = dbeta, dgamma) from the listed groups' compact dA, dA overwritten
- *       in place with the listed groups' conv-output gradient, gsum their row sums (row = position in the
- *       list, or the group id when gsum_by_group), uv[2][C].
+ *   bnrelu_backward_listed_apply (declared with rows_gemm_bnrelu_stats below): given S (the sums = dbeta, dgamma,
+ *       over the listed groups' compact dA), dA is overwritten in place with the listed groups' conv-output
+ *       gradient, gsum (nullable) receives their row sums (row = position in the list, or the group id when
+ *       gsum_by_group), uv[2][C] (nullable) the correction's u, v.  n_listed <= G.
  *   masked_group_sums: dgb[groups[cg]] = v * hs[cg] + 32 * xe[cg]: the row sums of dh over a masked group
  *       (hs = the group's summed conv output without its bias term, xe = u + v * gb).
  *   group_sum_listed: out[cg] = sum of the 32 rows of X's group groups[cg].
- *   linear_backward_weight_listed: dW[N,K] = sum_m dY[rowA(m)]^T X[rowB(m)], whole 32-row groups gathered on
- *       either operand (lists nullable = compact operand); dY = X with one list = a Gram matrix.
+ *   rows_wgrad_listed (declared with the weight gradients below): dW[N,K] = sum_m dY[rowA(m)]^T X[rowB(m)], whole
+ *       32-row groups gathered on either operand; dY = X with one list = a Gram matrix.
  *   group_gemm_scatter: Y[c_groups[m/32]*32 + m%32] = X[a_groups[m/32]*32 + m%32] . W[N,K]^T + gbias[m/32]
  *       (a_groups, gbias nullable); rows of Y outside the listed groups are not touched. */
-int pdae_bnrelu_backward_listed(int G, int C, float* dA, const float* X, const float* scale, const float* shift,
-                                const float* mean, const float* invstd, const float* gamma, float* S,
-                                float* gsum /*nullable*/, int gsum_by_group, float* uv /*nullable*/,
-                                int n_listed, const int32_t* groups, pdae_stream_t stream);
 int pdae_masked_group_sums(int n_listed, int C, const float* hs, const float* xe, const float* v,
                            const int32_t* groups, float* dgb, pdae_stream_t stream);
 int pdae_group_sum_listed(int n_listed, int C, const float* X, const int32_t* groups, float* out,
                           pdae_stream_t stream);
-int pdae_linear_backward_weight_listed(int M, int N, int K, const float* dY, const int32_t* a_groups,
-                                       const float* X, const int32_t* b_groups, float* dW,
-                                       float* dbias /*nullable*/, pdae_stream_t stream);
 int pdae_group_gemm_scatter(int M, int N, int K, const float* X, const int32_t* a_groups, const float* W,
                             const float* gbias, float* Y, int ldy, const int32_t* c_groups,
                             pdae_stream_t stream);
@@ -513,7 +485,7 @@ int pdae_group_gemm_scatter(int M, int N, int K, const float* X, const int32_t* 
  *       previous layer's BatchNorm + ReLU, relu(x*scale[k] + shift[k]), applied while
  *       X is staged (scale = shift = NULL: X as is).  The normalised activations are
  *       never stored.  Backward of a layer: bnrelu_backward, then
- *       bnrelu_linear_backward_weight / rows_gemm (w_kn) as in the patch embedder.
+ *       rows_wgrad_listed / rows_gemm (w_kn) as in the patch embedder.
  *   bnrelu_group_max: out[g][c] = max_j relu(y[g*ns+j][c]*scale[c] + shift[c]),
  *       arg[g][c] = the first j attaining it (ns <= 256).
  *   group_max_scatter_n: dense[g*ns+j][c] = (j == arg[g][c]) ? grad[g][c] : 0. */
@@ -627,9 +599,6 @@ int pdae_rows_wgrad_multi(int nprob, const int* Ms, const float* const* dY, cons
  * cuDNN 1x1 conv followed by separate BatchNorm / ReLU / max / concat passes
  * over (B*G*32, C) tensors.
  *
- *   embed_conv_store_groupmax   (first_conv[3] + the max of :47)
- *       Y[M,N] = X[M,K].W[N,K]^T + bias;  gmax[M/32,N] = max over each group's
- *       32 rows of Y, garg[M/32,N] (u8) = first row inside the group attaining it.
  *   embed_conv_groupbias_stats  (second_conv[0] on concat([global, local]), :48-49,
  *       with the weight split into its global / local halves)
  *       Y[M,N] = X[M,K].W[N,K]^T + gbias[M/32,N]   (gbias = global half + bias,
@@ -638,15 +607,11 @@ int pdae_rows_wgrad_multi(int nprob, const int* Ms, const float* const* dY, cons
  *       pass over Y.  stats is zero-filled by the call.
  *   embed_bnrelu_conv_groupmax  (second_conv[1..3] + the max of :50)
  *       gmax[M/32,N] = max over groups of (relu(X*scale + shift).W^T + bias),
- *       garg = argmax row; the (M,N) product itself is never written.
- *   bnrelu_linear_backward_weight
- *       dW[N,K] = dY[M,N]^T . relu(X[M,K]*scale + shift)  (activation recomputed
- *       while it is staged); dW is overwritten.
+ *       garg[M/32,N] (u8) = first row inside the group attaining it; the (M,N)
+ *       product itself is never written.
+ * The weight gradients of these layers, dW[N,K] = dY[M,N]^T . relu(X[M,K]*scale + shift)
+ * with the activation recomputed while it is staged, are rows_wgrad_listed's.
  */
-int pdae_embed_conv_store_groupmax(int M, int N, int K, const float* X,
-                                   const float* W, const float* bias, float* Y,
-                                   float* gmax, unsigned char* garg,
-                                   pdae_stream_t stream);
 int pdae_embed_conv_groupbias_stats(int M, int N, int K, const float* X,
                                     const float* W, const float* gbias,
                                     float* Y, float* stats,
@@ -657,21 +622,16 @@ int pdae_embed_bnrelu_conv_groupmax(int M, int N, int K, const float* X,
                                     float* gmax, unsigned char* garg,
                                     const int32_t* groups /*nullable*/,
                                     pdae_stream_t stream);
-int pdae_bnrelu_linear_backward_weight(int M, int N, int K, const float* dY,
-                                       const float* X, const float* scale,
-                                       const float* shift, float* dW,
-                                       float* dbias /*nullable: column sums of dY*/,
-                                       const int32_t* groups /*nullable*/,
-                                       pdae_stream_t stream);
-/* `groups` (embed_bnrelu_conv_groupmax, bnrelu_linear_backward_weight,
- * bnrelu_backward): a list of group (patch) ids.  The last conv of the embedder
+/* `groups` (embed_bnrelu_conv_groupmax, bnrelu_backward; b_groups of
+ * rows_wgrad_listed): a list of group (patch) ids.  The last conv of the embedder
  * comes after the last BatchNorm, and the tokens of masked patches are thrown
  * away by MaskTransformer.forward (:449), so only the VISIBLE patches need that
  * GEMM: with a list, the M = 32*len(groups) rows of the product are gathered
  * from X group-wise (row m <- X[groups[m/32]*32 + m%32]) and the outputs are
  * compact, in list order.  Same numbers as computing all patches and selecting. */
 /*   embed_bnrelu_conv_store_groupmax  (first_conv[1..3] + the max of :47)
- *       Y[M,N] = relu(X*scale + shift).W^T + bias, plus its group max / argmax. */
+ *       Y[M,N] = relu(X*scale + shift).W^T + bias;  gmax[M/32,N] = max over each
+ *       group's 32 rows of Y, garg = the first row attaining it. */
 int pdae_embed_bnrelu_conv_store_groupmax(int M, int N, int K, const float* X,
                                           const float* scale, const float* shift,
                                           const float* W, const float* bias,
@@ -744,8 +704,9 @@ int pdae_bnrelu_backward(int G, int C, float* dA, const float* X,
  *       rows_gemm_bnrelu_stats_workspace(M, N) floats (one partial row of sums per 128-row band; added in band order
  *       in fp64: no atomics, bit-identical run to run).  On the fp32-input arithmetic, or without a workspace, the
  *       entry runs the plain product and bnrelu_backward's own reduction sweep.
- *   bnrelu_backward_apply / bnrelu_backward_listed_apply   the second halves of bnrelu_backward / _listed for a caller
- *       that holds S already: same arguments, S is read. */
+ *   bnrelu_backward_apply   the second half of bnrelu_backward for a caller that holds S already: same arguments,
+ *       S is read.
+ *   bnrelu_backward_listed_apply   the same over a list of groups alone (the masked patches' algebra above). */
 long long pdae_rows_gemm_bnrelu_stats_workspace(int M, int N);
 int pdae_rows_gemm_bnrelu_stats(int M, int N, int K, const float* dY, const float* W, const float* X,
                                 const int32_t* groups /*nullable*/, const float* scale, const float* shift,

@@ -42,9 +42,6 @@ _SIGNATURES = {
     "pdae_chamfer_backward": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_chamfer_backward_mean": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_mean_sum2": [ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
-    "pdae_linear_forward": [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp],
-    "pdae_linear_backward_data": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_linear_backward_weight": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pdae_rows_gemm": [_i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
     "pdae_rows_gemm_batched": [_i, _i, _i, _i, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp],
     "pdae_rows_wgrad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -52,10 +49,8 @@ _SIGNATURES = {
     "pdae_rows_wgrad_listed": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_sa_group_rows": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_sa_group_rows_grad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_embed_conv_store_groupmax": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_conv_groupbias_stats": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_bnrelu_conv_groupmax": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_bnrelu_linear_backward_weight": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_bnrelu_conv_store_groupmax": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_group_max_scatter": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_group_scatter_add": [_i, _i, _vp, _vp, _vp, _vp],
@@ -82,10 +77,8 @@ _SIGNATURES = {
     "pdae_embed_conv1_backward_weight": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_bn_finalize": [_i, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_adamw_step": [ctypes.c_longlong, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp],
-    "pdae_bnrelu_backward_listed": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp],
     "pdae_masked_group_sums": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_group_sum_listed": [_i, _i, _vp, _vp, _vp, _vp],
-    "pdae_linear_backward_weight_listed": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_group_gemm_scatter": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "pdae_conv_stats": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_bnrelu_group_max": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -157,7 +150,6 @@ _HOST = {
     "pdae_rows_wgrad_multi_workspace": [_i, _vp, _vp, _vp, _vp],
     "pdae_set_deterministic": [_vp, ctypes.c_size_t],
     "pdae_deferred_begin": [_vp, ctypes.c_size_t],
-    "pdae_deferred_hold": [_i],
     "pdae_fold_input_grad_parts": [_i, _i],
     "pdae_embed_conv1_backward_weight_parts": [_i],
     "pdae_fold_out_backward_parts": [ctypes.c_longlong],

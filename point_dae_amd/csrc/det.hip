@@ -30,7 +30,7 @@ struct Ctx {
   size_t ws_bytes = 0;
   float* def_ws = nullptr;            // deferred reductions
   size_t def_floats = 0, def_used = 0;
-  bool def_on = false, def_hold = false;
+  bool def_on = false;
   DefJobs def_jobs;
   int def_n = 0;
   int arith = -1;                     // GEMM arithmetic (-1: PDAE_GEMM in the environment decides at first use)
@@ -93,7 +93,7 @@ int det_reduce_f64(hipStream_t s, int P, int width, const double* part, double* 
 }
 
 // ---- deferred reductions ---------------------------------------------------------------------
-bool deferred_on() { return ctx().def_on && !ctx().def_hold; }
+bool deferred_on() { return ctx().def_on; }
 
 float* deferred_take(int P, int width, float* o0, int n0, float* o1, int n1, float* o2, int n2) {
   Ctx& c = ctx();
@@ -153,7 +153,7 @@ extern "C" int pdae_deferred_begin(void* workspace, size_t bytes) {
   pdae::Ctx& c = pdae::ctx();
   c.def_ws = static_cast<float*>(workspace);
   c.def_floats = bytes / sizeof(float);
-  c.def_used = 0, c.def_n = 0, c.def_on = true, c.def_hold = false;
+  c.def_used = 0, c.def_n = 0, c.def_on = true;
   return PDAE_OK;
 }
 
@@ -170,11 +170,6 @@ extern "C" int pdae_deferred_flush(pdae_stream_t stream) {
                      c.def_jobs);
   c.def_n = 0;
   return check_launch("deferred_flush");
-}
-
-extern "C" int pdae_deferred_hold(int hold) {
-  pdae::ctx().def_hold = hold != 0;
-  return PDAE_OK;
 }
 
 extern "C" int pdae_ctx_create(pdae_ctx_t* out) {

@@ -381,9 +381,10 @@ int bnrelu_backward_sums(hipStream_t s, int Rsum, int C, const float* dA, const 
 }
 }  // namespace pdae
 
-// The apply halves of pdae_bnrelu_backward / pdae_bnrelu_backward_listed for a caller that already holds the sums S (from
-// pdae_rows_gemm_bnrelu_stats: the data-gradient GEMM that produced dA left them): same arguments, S is an INPUT.  dA may
-// already carry the ReLU mask (the apply re-evaluates it: idempotent).
+// The apply halves of BatchNorm + ReLU backward for a caller that already holds the sums S (from
+// pdae_rows_gemm_bnrelu_stats: the data-gradient GEMM that produced dA left them): pdae_bnrelu_backward's arguments with S
+// an INPUT, over all groups or -- the _listed form -- over a list of them.  dA may already carry the ReLU mask (the apply
+// re-evaluates it: idempotent).
 extern "C" int pdae_bnrelu_backward_apply(int G, int C, float* dA, const float* X, const float* scale,
                                           const float* shift, const float* mean, const float* invstd,
                                           const float* gamma, const float* S, float* gsum, int n_listed,
@@ -486,43 +487,6 @@ extern "C" int pdae_bn_finalize(int C, long long rows, const double* stats64, co
                      (double)rows, stats64, partials, P, gamma, beta, eps, momentum, running_mean,
                      running_var, num_batches_tracked, scale, shift, mean, invstd);
   return check_launch("bn_finalize");
-}
-
-extern "C" int pdae_bnrelu_backward_listed(int G, int C, float* dA, const float* X, const float* scale,
-                                           const float* shift, const float* mean, const float* invstd,
-                                           const float* gamma, float* S, float* gsum, int gsum_by_group,
-                                           float* uv, int n_listed, const int32_t* groups,
-                                           pdae_stream_t stream) {
-  if (G < 0 || n_listed < 0 || n_listed > G || C <= 0 || C % 4 != 0)
-    return bad_arg("bnrelu_backward_listed: C must be a positive multiple of 4, n_listed <= G");
-  if (!S) return bad_arg("bnrelu_backward_listed: null pointer");
-  hipStream_t s = as_stream(stream);
-  (void)hipMemsetAsync(S, 0, sizeof(float) * 2 * (size_t)C, s);
-  if (!scale || !shift || !mean || !invstd || !gamma || (n_listed && (!dA || !X || !groups)))
-    return bad_arg("bnrelu_backward_listed: null pointer");
-  const int Rsum = n_listed * 32;
-  int rc = PDAE_OK;
-  if (Rsum > 0) {
-    int rows = 512;
-    int by = (Rsum + rows - 1) / rows;
-    if (by > 16384) {
-      rows = (Rsum + 16383) / 16384;
-      by = (Rsum + rows - 1) / rows;
-    }
-    float* det = static_cast<float*>(det_workspace(sizeof(float) * (size_t)by * 2 * C, &rc));
-    if (rc) return rc;
-    hipLaunchKernelGGL(bnrelu_backward_reduce_kernel, dim3((C / 4 + 31) / 32, by), dim3(256), 0, s, Rsum, C, dA, X,
-                       scale, shift, mean, invstd, S, rows, groups, det);
-    if (det && (rc = det_reduce(s, by, 2 * C, det, S, 2 * C))) return rc;
-  }
-  const float inv_rows = G > 0 ? 1.0f / (float)((long long)G * 32) : 0.f;
-  if (n_listed > 0)
-    hipLaunchKernelGGL(bnrelu_backward_apply_listed_kernel, dim3((C / 4 + 31) / 32, (n_listed + 7) / 8), dim3(256), 0,
-                       s, n_listed, C, dA, X, scale, shift, mean, invstd, gamma, S, inv_rows, gsum, groups, gsum_by_group);
-  if (uv)
-    hipLaunchKernelGGL(bn_correction_kernel, dim3((C + 255) / 256), dim3(256), 0, s, C, S, inv_rows, gamma, mean,
-                       invstd, uv);
-  return check_launch("bnrelu_backward_listed");
 }
 
 extern "C" int pdae_group_sum_listed(int n_listed, int C, const float* X, const int32_t* groups, float* out,

@@ -1,13 +1,15 @@
-// gemm.hip -- fp32 GEMMs on the gfx950 matrix cores (v_mfma_f32_32x32x2_f32),
-// with the producer / epilogue fusions the patch embedder needs.
+// gemm.hip -- the fp32-input NT GEMM on the gfx950 matrix cores (v_mfma_f32_32x32x2_f32) with the producer / epilogue
+// fusions of the patch embedder and of the set-abstraction MLPs, and the K = 4 pass of a set-abstraction level's
+// first layer.
 //
-// The reference runs its dense layers (nn.Linear / 1x1 nn.Conv1d: patch
-// embedder models/PointCAE_transformer.py:24-51, attention and MLP :113-137,
-// :94-110, heads :329-333, :653-658) through cuBLAS/cuDNN in fp32, with
-// BatchNorm / ReLU / max-pool / concat as separate full passes over
-// (B*G*32, 512) tensors (537 MB each at B=128).  The fp32 MFMA of CDNA4 is exact
-// fp32 (a k-ordered fmaf chain) at the fp32 vector peak (157 TFLOP/s), so the
-// same arithmetic class is kept -- no TF32/bf16.
+// The entries below are the fused dense layers of the embedder (models/PointCAE_transformer.py:24-51) and of the
+// shared MLPs: BatchNorm / ReLU / max-pool / concat, separate full passes over (B*G*32, 512) tensors in the
+// reference (537 MB each at B=128), ride on the product as producers and epilogues.  Each entry builds an NtArgs and
+// hands it to the exact-split bf16 kernel of the same contracts (rows3_kernel.h conv3_kernel, through
+// rows3::conv3_takes / launch_conv3) -- the default arithmetic -- or to gemm_nt_kernel below: under
+// PDAE_GEMM=f32mfma, and in either arithmetic when K % 32 != 0.  The fp32 MFMA of CDNA4 is exact fp32 (a k-ordered
+// fmaf chain) at the fp32 vector peak (157 TFLOP/s): the reference's arithmetic class, no TF32/bf16.  No float
+// atomics in any product; the BatchNorm column statistics alone use them outside deterministic mode.
 //
 // Kernel "NT":  C[M,N] = epi( pro(A)[M,K] . B[N,K]^T )          (both K-contiguous)
 //   - block tile BM x BN (256x256 with 16 waves, 128x384 with 12, or 128x128 with 4),
@@ -30,20 +32,20 @@
 //     through the LDS double buffer, so a tile boundary costs only the epilogue.
 //   producers (applied to A while it is staged):
 //     PRO_BNRELU   a := max(0, a * scale[k] + shift[k])   -- BatchNorm + ReLU of
-//                  the previous layer never materialised
+//                  the previous layer never materialised; optional gather of whole
+//                  32-row groups (a_groups)
 //   epilogues:
-//     EPI_BIAS[_RELU|_GELU]  C = act(acc + bias[n])
 //     EPI_GROUPBIAS_STATS    C = acc + gbias[m/32][n]; per-column sum / sum of
 //                            squares of C accumulated into stats (BatchNorm
 //                            batch statistics without another pass over C)
+//     EPI_STATS              C = acc (+ bias[n]) with the same statistics
 //     EPI_GROUPMAX           out[m/32][n] = max over the 32 rows of a group of
 //                            (acc + bias[n]), arg[m/32][n] = first row attaining
 //                            it; C itself is never written (max-pool fused)
 //     EPI_STORE_GROUPMAX     both C = acc + bias and the group max / argmax
-// Kernel "TN":  C[N,K] = A[M,N]^T . B[M,K]   (weight gradients; reduction over
-//     the slow index M, split across blocks -- exactly one residency of the chip,
-//     all tiles of a split on one XCD -- fp32 atomics into C; optional producer on
-//     B, group-list row gather, fused column sums of A = the bias gradient).
+//     EPI_GROUP_SCATTER      C[c_groups[m/32]*32 + m%32] = acc + gbias[m/32][n]
+// Pass "K = 4" (conv_k4_stats_kernel): the first layer of a set-abstraction level on coordinates alone -- its (M, N)
+//     store is all there is; see the kernel.
 #include <type_traits>
 #include <cstdlib>
 
@@ -65,9 +67,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int GBK = 32, GLD = GBK + 4;
 
 __device__ __forceinline__ float act_relu(float v) { return v > 0.f ? v : 0.f; }
-__device__ __forceinline__ float act_gelu(float v) {
-  return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-}
 
 template <int BM, int BN, int PRO, int EPI>
 __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64) void gemm_nt_kernel(const NtArgs p) {
@@ -283,8 +282,6 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64) void gemm_nt_kernel(con
           const int lr = (e & 3) + 8 * (e >> 2) + 4 * h;
           const int row = rbase + lr;
           float v = acc[i][j][e] + add;
-          if (EPI == EPI_BIAS_RELU) v = act_relu(v);
-          if (EPI == EPI_BIAS_GELU) v = act_gelu(v);
           if ((EPI == EPI_GROUPBIAS_STATS || EPI == EPI_STATS) && (FULL || row < M)) {
             csum[j] += v;
             csq[j] += v * v;
@@ -355,210 +352,6 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64) void gemm_nt_kernel(con
   }   // persistent tile loop
 }
 
-// ---------------------------------------------------------------------------
-// C[N,K] += sum_m A[m,n] B[m,k] over this block's slice of M.  Tiles are read
-// "down the columns": lane (r,h) of MFMA step t takes A[m = 2t + h][n = i0 + r].
-// Optional producer on B (PRO_BNRELU over B's columns k) recomputes the
-// activation that was never stored.
-#ifndef PDAE_TBK
-#define PDAE_TBK 16
-#endif
-constexpr int TBK = PDAE_TBK;
-constexpr int TN_RES = TBK == 16 ? 3 : 2;   // TN blocks resident per CU (LDS: 32 KB / 64 KB each)
-struct TnArgs {
-  int M, N, K;
-  const float* A;
-  int lda;
-  const float* B;
-  int ldb;
-  float* C;
-  int ldc;
-  const float* pro_scale;  // [K]
-  const float* pro_shift;
-  const int* b_groups;     // nullable: row m of B is source row b_groups[m/32]*32 + m%32
-  const int* a_groups;     // nullable: the same for A
-  float* colsum_a;         // nullable: [N] += column sums of A (the bias gradient), from the k-tile-0 blocks
-  int rows_per_split;
-  int tk, tn, splits;      // tiles along K and N, M-splits
-  float* part_c;           // deterministic mode: [splits][N][K] plain-store partials (else null)
-  float* part_s;           //                     [splits][N] partials of colsum_a
-};
-
-// Block tile TM (columns n of A) x TN_ (columns k of B); every wave 64x64.  Bigger
-// tiles = fewer bytes staged per MAC (the 128x128 version ran at 69 TFLOP/s).
-template <int TM, int TN_, int PRO>
-__global__ __launch_bounds__((TM / 64) * (TN_ / 64) * 64) __attribute__((amdgpu_waves_per_eu(TN_RES, TN_RES)))
-void gemm_tn_kernel(const TnArgs p) {
-  constexpr int WN = TN_ / 64;
-  constexpr int NT = (TM / 64) * (TN_ / 64) * 64;
-  constexpr int ROW4 = (TM + TN_) / 4;              // float4 per staged row
-  constexpr int SLOTS = (TBK * ROW4 + NT - 1) / NT;  // float4 per thread per tile
-  __shared__ float lds[2][TBK * (TM + TN_)];
-  // XCD-aware order (1-D grid; blocks b, b+8, ... share an L2): all tn*tk tiles of one
-  // M-split are consecutive slots of ONE XCD, so they run together and the tk-fold re-read
-  // of the A band and the tn-fold re-read of the B band hit that L2 instead of HBM
-  // (PMC before: dW3 fetched 2.2 GB for 0.8 GB of operands).
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int tiles = p.tk * p.tn;
-  const int tile = slot % tiles, split = (slot / tiles) * 8 + xcd;
-  if (split >= p.splits) return;
-  const int bx = tile % p.tk, by = tile / p.tk;
-  const int n0 = by * TM, k0 = bx * TN_;
-  const int mbeg = split * p.rows_per_split;
-  const int mend = min(p.M, mbeg + p.rows_per_split);
-  if (mbeg >= mend) return;
-  const int N = p.N, K = p.K;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int r = lane & 31, h = lane >> 5;
-
-  // NT is a multiple of ROW4, so a thread stages the SAME four columns in every slot
-  // (one scale/shift float4, not one per slot: 56 VGPRs less, three blocks per CU)
-  static_assert(NT % ROW4 == 0 && (TBK * ROW4) % NT == 0, "slot layout");
-  constexpr int RSTEP = NT / ROW4;
-  const int srow0 = tid / ROW4, scol = (tid % ROW4) * 4;
-  const bool isb = scol >= TM;
-  const int gcol = isb ? k0 + scol - TM : n0 + scol;
-  const bool ok = isb ? gcol < K : gcol < N;
-  float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (PRO == PRO_BNRELU && isb && ok) {
-    sc = *reinterpret_cast<const float4*>(p.pro_scale + gcol);
-    sh = *reinterpret_cast<const float4*>(p.pro_shift + gcol);
-  }
-  const float* src = isb ? p.B + gcol : p.A + gcol;
-  const int ld = isb ? p.ldb : p.lda;
-  float4 rg[SLOTS];
-  bool rin[SLOTS];
-  float4 asum = make_float4(0.f, 0.f, 0.f, 0.f);   // column sums of this thread's A elements
-  const bool sum_a = p.colsum_a != nullptr && bx == 0 && !isb;
-  static_assert(32 % TBK == 0, "a staged slab lies inside one 32-row group");
-  auto gload = [&](int mt) {
-    // a slab is TBK consecutive rows starting at a multiple of TBK: inside ONE group of the
-    // list -> one uniform (scalar) id load per slab instead of a dependent load per slot
-    const int shift = p.b_groups ? (__builtin_amdgcn_readfirstlane(p.b_groups[mt >> 5]) * 32 - (mt & ~31)) : 0;
-    const int shift_a = p.a_groups ? (__builtin_amdgcn_readfirstlane(p.a_groups[mt >> 5]) * 32 - (mt & ~31)) : 0;
-#pragma unroll
-    for (int i = 0; i < SLOTS; ++i) {
-      const int gm = mt + srow0 + i * RSTEP;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (ok && gm < mend) {
-        const int sm = isb ? gm + shift : gm + shift_a;
-        v = *reinterpret_cast<const float4*>(src + (size_t)sm * ld);
-      }
-      rg[i] = v;
-      rin[i] = ok && gm < mend;
-    }
-  };
-  // producer math and the bias-gradient sums run here, AFTER the MFMA loop: the loads issued
-  // by gload stay in flight behind the MFMAs instead of being waited for right away
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < SLOTS; ++i) {
-      float4 v = rg[i];
-      if (PRO == PRO_BNRELU && isb && rin[i]) {
-        v.x = act_relu(v.x * sc.x + sh.x);
-        v.y = act_relu(v.y * sc.y + sh.y);
-        v.z = act_relu(v.z * sc.z + sh.z);
-        v.w = act_relu(v.w * sc.w + sh.w);
-      }
-      if (sum_a) asum.x += v.x, asum.y += v.y, asum.z += v.z, asum.w += v.w;
-      *reinterpret_cast<float4*>(&lds[buf][(srow0 + i * RSTEP) * (TM + TN_) + scol]) = v;
-    }
-  };
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  gload(mbeg);
-  lstore(0);
-  __syncthreads();
-  int buf = 0;
-  for (int mt = mbeg; mt < mend; mt += TBK) {
-    if (mt + TBK < mend) gload(mt + TBK);
-    const float* T = lds[buf] + h * (TM + TN_);
-    // fragment reads run two k-steps ahead of the MFMAs that consume them
-    float fa[2][2][2], fb[2][2][2];   // [stage][step within stage][tile]
-    auto fread = [&](int st, int t) {
-      const float* row = T + 2 * t * (TM + TN_);
-      fa[st][t & 1][0] = row[wm * 64 + r];
-      fa[st][t & 1][1] = row[wm * 64 + 32 + r];
-      fb[st][t & 1][0] = row[TM + wn * 64 + r];
-      fb[st][t & 1][1] = row[TM + wn * 64 + 32 + r];
-    };
-    fread(0, 0);
-    fread(0, 1);
-#pragma unroll
-    for (int tt = 0; tt < TBK / 4; ++tt) {
-      const int cur = tt & 1, nxt = cur ^ 1;
-      if (tt + 1 < TBK / 4) {
-        fread(nxt, 2 * tt + 2);
-        fread(nxt, 2 * tt + 3);
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][u][0], fb[cur][u][0], acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][u][0], fb[cur][u][1], acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][u][1], fb[cur][u][0], acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][u][1], fb[cur][u][1], acc[1][1], 0, 0, 0);
-      }
-      // issue order (see gemm_nt_kernel): the next slab's global loads behind the first MFMAs,
-      // one fragment read behind every MFMA, the LDS stores of the next slab behind the last ones
-      if (tt == 0) __builtin_amdgcn_sched_group_barrier(0x020, SLOTS, 0);
-#pragma unroll
-      for (int g = 0; g < 8; ++g) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if (tt + 1 < TBK / 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        else if (g < SLOTS) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-      }
-      if (tt == TBK / 4 - 2 && mt + TBK < mend) lstore(buf ^ 1);
-    }
-    __syncthreads();
-    buf ^= 1;
-  }
-  if (p.colsum_a != nullptr && bx == 0) {
-    // the RSTEP threads that staged the same four columns meet in LDS (free after the loop's
-    // last barrier) and are added in row-phase order
-    float4* ls = reinterpret_cast<float4*>(&lds[0][0]);   // [RSTEP][TM / 4]
-    if (!isb) ls[srow0 * (TM / 4) + scol / 4] = asum;
-    __syncthreads();
-    if (!isb && srow0 == 0 && ok) {
-      float4 t = ls[scol / 4];
-#pragma unroll
-      for (int k = 1; k < RSTEP; ++k) {
-        const float4 u = ls[k * (TM / 4) + scol / 4];
-        t.x += u.x, t.y += u.y, t.z += u.z, t.w += u.w;
-      }
-      if (p.part_s) {
-        *reinterpret_cast<float4*>(p.part_s + (size_t)split * N + gcol) = t;
-      } else {
-        atomicAdd(p.colsum_a + gcol + 0, t.x), atomicAdd(p.colsum_a + gcol + 1, t.y);
-        atomicAdd(p.colsum_a + gcol + 2, t.z), atomicAdd(p.colsum_a + gcol + 3, t.w);
-      }
-    }
-  }
-  float* pc = p.part_c ? p.part_c + (size_t)split * N * K : nullptr;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = k0 + wn * 64 + j * 32 + r;
-    if (col >= K) continue;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = n0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (row < N) {
-          if (pc) pc[(size_t)row * K + col] = acc[i][j][e];
-          else atomicAdd(p.C + (size_t)row * p.ldc + col, acc[i][j][e]);
-        }
-      }
-    }
-  }
-}
-
 template <int BM, int BN, int PRO, int EPI>
 static void launch_nt_cfg(NtArgs& a, hipStream_t s) {
   const int tiles_m = (a.M + BM - 1) / BM;
@@ -613,105 +406,7 @@ static int check_nt(const char* who, int M, int N, int K) {
 
 using namespace pdae;
 
-extern "C" int pdae_linear_forward(int M, int N, int K, const float* X, const float* W,
-                                   const float* bias, int act, float* Y, pdae_stream_t stream) {
-  int rc = check_nt("linear_forward: bad size", M, N, K);
-  if (rc) return rc;
-  if (act < 0 || act > 2) return bad_arg("linear_forward: act must be 0, 1 or 2");
-  if (M == 0) return PDAE_OK;
-  if (!X || !W || !Y) return bad_arg("linear_forward: null pointer");
-  NtArgs a = {};
-  a.M = M, a.N = N, a.K = K, a.A = X, a.lda = K, a.B = W, a.ldb = K, a.C = Y, a.ldc = N, a.bias = bias;
-  hipStream_t s = as_stream(stream);
-  if (act == 0) return launch_nt<PRO_NONE, EPI_BIAS>(a, s);
-  if (act == 1) return launch_nt<PRO_NONE, EPI_BIAS_RELU>(a, s);
-  return launch_nt<PRO_NONE, EPI_BIAS_GELU>(a, s);
-}
-
-extern "C" int pdae_linear_backward_data(int M, int N, int K, const float* dY, const float* Wt,
-                                         float* dX, pdae_stream_t stream) {
-  // dX[M,K] = dY[M,N] . W[N,K]  ==  NT product with W^T [K,N] (N contiguous)
-  int rc = check_nt("linear_backward_data: bad size", M, K, N);
-  if (rc) return rc;
-  if (M == 0) return PDAE_OK;
-  if (!dY || !Wt || !dX) return bad_arg("linear_backward_data: null pointer");
-  NtArgs a = {};
-  a.M = M, a.N = K, a.K = N, a.A = dY, a.lda = N, a.B = Wt, a.ldb = N, a.C = dX, a.ldc = K;
-  return launch_nt<PRO_NONE, EPI_BIAS>(a, as_stream(stream));
-}
-
-template <int TM, int TN_>
-static int launch_tn_cfg(TnArgs& t, bool bnrelu, hipStream_t s) {
-  const int tn = (t.N + TM - 1) / TM, tk = (t.K + TN_ - 1) / TN_;
-  constexpr int NTH = (TM / 64) * (TN_ / 64) * 64;
-  // M-splits so that the grid is ONE full residency of the chip (256 CUs x 3 blocks):
-  // 768 blocks ran dW4 in 576 us, 1024 blocks (1.33 rounds) in 663 us; each split >= 256 rows
-  int splits = (TN_RES * 256 + tn * tk / 2) / (tn * tk);
-  if (splits < 1) splits = 1;
-  int rows = (t.M + splits - 1) / splits;
-  rows = ((rows + TBK - 1) / TBK) * TBK;
-  if (rows < 256) rows = 256;
-  splits = (t.M + rows - 1) / rows;
-  t.rows_per_split = rows;
-  t.tk = tk, t.tn = tn, t.splits = splits;
-  const unsigned grid = 8u * ((splits + 7) / 8) * tk * tn;
-  // deterministic mode: the splits store their tiles side by side and one pass adds them in
-  // split order (the zero-filled dW / dbias receive the sums)
-  int rc = PDAE_OK;
-  const size_t nk = (size_t)t.N * t.K;
-  float* ws = static_cast<float*>(det_workspace(sizeof(float) * splits * (nk + t.N), &rc));
-  if (rc) return rc;
-  if (ws) t.part_c = ws, t.part_s = ws + splits * nk;
-  if (bnrelu)
-    hipLaunchKernelGGL((gemm_tn_kernel<TM, TN_, PRO_BNRELU>), dim3(grid), dim3(NTH), 0, s, t);
-  else
-    hipLaunchKernelGGL((gemm_tn_kernel<TM, TN_, PRO_NONE>), dim3(grid), dim3(NTH), 0, s, t);
-  if (ws) {
-    if (t.ldc != t.K) return unsupported("deterministic mode: weight gradients with a dense leading dimension only");
-    if ((rc = det_reduce(s, splits, (int)nk, t.part_c, t.C, (int)nk))) return rc;
-    if (t.colsum_a && (rc = det_reduce(s, splits, t.N, t.part_s, t.colsum_a, t.N))) return rc;
-  }
-  return PDAE_OK;
-}
-
-static int launch_tn(TnArgs& t, bool bnrelu, hipStream_t s) {
-  // measured on the embedder's weight gradients (M = 262144): the 128x128 tile at two
-  // blocks per CU (654 us for dW4) beats 192x256 / 256x256 at one block per CU (767 us)
-  const int rc = launch_tn_cfg<128, 128>(t, bnrelu, s);
-  return rc ? rc : check_launch("gemm_tn");
-}
-
-extern "C" int pdae_linear_backward_weight(int M, int N, int K, const float* dY, const float* X,
-                                           float* dW, float* dbias, pdae_stream_t stream) {
-  if (M < 0 || N <= 0 || K <= 0) return bad_arg("linear_backward_weight: bad size");
-  if (!dW) return bad_arg("linear_backward_weight: null pointer");
-  hipStream_t s = as_stream(stream);
-  (void)hipMemsetAsync(dW, 0, sizeof(float) * (size_t)N * K, s);
-  if (dbias) (void)hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)N, s);
-  if (M == 0) return check_launch("linear_backward_weight");
-  if (!dY || !X) return bad_arg("linear_backward_weight: null pointer");
-  if (N % 4 != 0 || K % 4 != 0) return unsupported("linear_backward_weight: N, K multiples of 4");
-  TnArgs t = {};
-  t.M = M, t.N = N, t.K = K, t.A = dY, t.lda = N, t.B = X, t.ldb = K, t.C = dW, t.ldc = K;
-  t.colsum_a = dbias;      // the bias gradient rides on the A tiles the k-tile-0 blocks stage anyway
-  return launch_tn(t, false, s);
-}
-
 // ---- fused patch-embedder layers (models/PointCAE_transformer.py:37-51) ------
-extern "C" int pdae_embed_conv_store_groupmax(int M, int N, int K, const float* X, const float* W,
-                                              const float* bias, float* Y, float* gmax,
-                                              unsigned char* garg, pdae_stream_t stream) {
-  int rc = check_nt("embed_conv_store_groupmax: bad size", M, N, K);
-  if (rc) return rc;
-  if (M % 32 != 0) return bad_arg("embed_conv_store_groupmax: M must be a multiple of 32");
-  if (M == 0) return PDAE_OK;
-  if (!X || !W || !Y || !gmax || !garg) return bad_arg("embed_conv_store_groupmax: null pointer");
-  NtArgs a = {};
-  a.M = M, a.N = N, a.K = K, a.A = X, a.lda = K, a.B = W, a.ldb = K, a.C = Y, a.ldc = N, a.bias = bias;
-  a.gmax = gmax, a.garg = garg;
-  return launch_nt<PRO_NONE, EPI_STORE_GROUPMAX>(a, as_stream(stream));
-}
-
 extern "C" int pdae_embed_conv_groupbias_stats(int M, int N, int K, const float* X, const float* W,
                                                const float* gbias, float* Y, float* stats,
                                                pdae_stream_t stream) {
@@ -841,46 +536,6 @@ extern "C" int pdae_embed_bnrelu_conv_groupmax(int M, int N, int K, const float*
   a.M = M, a.N = N, a.K = K, a.A = X, a.lda = K, a.B = W, a.ldb = K, a.bias = bias;
   a.pro_scale = scale, a.pro_shift = shift, a.gmax = gmax, a.garg = garg, a.a_groups = groups;
   return launch_nt<PRO_BNRELU, EPI_GROUPMAX>(a, as_stream(stream));
-}
-
-extern "C" int pdae_bnrelu_linear_backward_weight(int M, int N, int K, const float* dY,
-                                                  const float* X, const float* scale,
-                                                  const float* shift, float* dW, float* dbias,
-                                                  const int32_t* groups, pdae_stream_t stream) {
-  if (M < 0 || N <= 0 || K <= 0) return bad_arg("bnrelu_linear_backward_weight: bad size");
-  if (!dW) return bad_arg("bnrelu_linear_backward_weight: null pointer");
-  hipStream_t s = as_stream(stream);
-  (void)hipMemsetAsync(dW, 0, sizeof(float) * (size_t)N * K, s);
-  if (dbias) (void)hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)N, s);
-  if (M == 0) return check_launch("bnrelu_linear_backward_weight");
-  if (!dY || !X || !scale || !shift) return bad_arg("bnrelu_linear_backward_weight: null pointer");
-  if (N % 4 != 0 || K % 4 != 0) return unsupported("bnrelu_linear_backward_weight: N, K multiples of 4");
-  TnArgs t = {};
-  t.M = M, t.N = N, t.K = K, t.A = dY, t.lda = N, t.B = X, t.ldb = K, t.C = dW, t.ldc = K;
-  t.pro_scale = scale, t.pro_shift = shift, t.b_groups = groups, t.colsum_a = dbias;
-  if (groups && M % 32 != 0) return bad_arg("bnrelu_linear_backward_weight: M must be a multiple of 32 with a group list");
-  return launch_tn(t, true, s);
-}
-
-// dW[N,K] = sum over listed rows of dY[rowA(m)]^T X[rowB(m)]: the TN kernel with whole 32-row groups gathered
-// on either operand (a_groups / b_groups nullable: that operand is compact).  dY = X = f with the same list on
-// both sides is the Gram matrix of the listed rows.
-extern "C" int pdae_linear_backward_weight_listed(int M, int N, int K, const float* dY, const int32_t* a_groups,
-                                                  const float* X, const int32_t* b_groups, float* dW,
-                                                  float* dbias, pdae_stream_t stream) {
-  if (M < 0 || N <= 0 || K <= 0) return bad_arg("linear_backward_weight_listed: bad size");
-  if (!dW) return bad_arg("linear_backward_weight_listed: null pointer");
-  if (M % 32 != 0) return bad_arg("linear_backward_weight_listed: M must be a multiple of 32 (whole groups)");
-  hipStream_t s = as_stream(stream);
-  (void)hipMemsetAsync(dW, 0, sizeof(float) * (size_t)N * K, s);
-  if (dbias) (void)hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)N, s);
-  if (M == 0) return check_launch("linear_backward_weight_listed");
-  if (!dY || !X) return bad_arg("linear_backward_weight_listed: null pointer");
-  if (N % 4 != 0 || K % 4 != 0) return unsupported("linear_backward_weight_listed: N, K multiples of 4");
-  TnArgs t = {};
-  t.M = M, t.N = N, t.K = K, t.A = dY, t.lda = N, t.B = X, t.ldb = K, t.C = dW, t.ldc = K;
-  t.a_groups = a_groups, t.b_groups = b_groups, t.colsum_a = dbias;
-  return launch_tn(t, false, s);
 }
 
 // Y[c_groups[m/32]*32 + m%32, :] = X[a_groups[m/32]*32 + m%32, :] . W[N,K]^T + gbias[m/32, :] for the M rows

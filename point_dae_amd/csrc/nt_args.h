@@ -7,9 +7,6 @@ namespace pdae {
 
 enum { PRO_NONE = 0, PRO_BNRELU = 1 };
 enum {
-  EPI_BIAS = 0,
-  EPI_BIAS_RELU = 1,
-  EPI_BIAS_GELU = 2,
   EPI_GROUPBIAS_STATS = 3,
   EPI_GROUPMAX = 4,
   EPI_STORE_GROUPMAX = 5,

@@ -23,32 +23,31 @@ static void conv3_launch(NtArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k, dim3(8 * nslots), dim3(512), lds, s, a);
 }
 
+// the (producer, epilogue) pairs gemm.hip asks for: the only instantiations of conv3_kernel
+static bool conv3_pair(int pro, int epi) {
+  if (pro == PRO_NONE) return epi == EPI_GROUPBIAS_STATS || epi == EPI_STATS || epi == EPI_GROUP_SCATTER;
+  return pro == PRO_BNRELU && (epi == EPI_STATS || epi == EPI_GROUPMAX || epi == EPI_STORE_GROUPMAX);
+}
+
 bool conv3_takes(const NtArgs& a, int pro, int epi) {
-  (void)pro;
+  if (!conv3_pair(pro, epi)) return false;
   if (a.K % 32 != 0 || a.K < 32 || a.M <= 0) return false;
-  const bool group_epi = epi == EPI_GROUPBIAS_STATS || epi == EPI_GROUPMAX || epi == EPI_STORE_GROUPMAX || epi == EPI_GROUP_SCATTER;
-  if ((group_epi || a.a_groups) && a.M % 32 != 0) return false;
-  return epi == EPI_BIAS || epi == EPI_STATS || group_epi;
+  const bool group_epi = epi != EPI_STATS;                     // every other epilogue works on whole 32-row groups
+  return !(group_epi || a.a_groups) || a.M % 32 == 0;
 }
 
 void launch_conv3(NtArgs& a, int pro, int epi, hipStream_t s) {
   if (pro == PRO_NONE) {
     switch (epi) {
-      case EPI_BIAS: conv3_launch<PRO_NONE, EPI_BIAS>(a, s); break;
       case EPI_GROUPBIAS_STATS: conv3_launch<PRO_NONE, EPI_GROUPBIAS_STATS>(a, s); break;
       case EPI_STATS: conv3_launch<PRO_NONE, EPI_STATS>(a, s); break;
-      case EPI_STORE_GROUPMAX: conv3_launch<PRO_NONE, EPI_STORE_GROUPMAX>(a, s); break;
-      case EPI_GROUPMAX: conv3_launch<PRO_NONE, EPI_GROUPMAX>(a, s); break;
-      default: conv3_launch<PRO_NONE, EPI_GROUP_SCATTER>(a, s); break;
+      case EPI_GROUP_SCATTER: conv3_launch<PRO_NONE, EPI_GROUP_SCATTER>(a, s); break;
     }
   } else {
     switch (epi) {
-      case EPI_BIAS: conv3_launch<PRO_BNRELU, EPI_BIAS>(a, s); break;
       case EPI_STATS: conv3_launch<PRO_BNRELU, EPI_STATS>(a, s); break;
-      case EPI_STORE_GROUPMAX: conv3_launch<PRO_BNRELU, EPI_STORE_GROUPMAX>(a, s); break;
       case EPI_GROUPMAX: conv3_launch<PRO_BNRELU, EPI_GROUPMAX>(a, s); break;
-      case EPI_GROUPBIAS_STATS: conv3_launch<PRO_BNRELU, EPI_GROUPBIAS_STATS>(a, s); break;
-      default: conv3_launch<PRO_BNRELU, EPI_GROUP_SCATTER>(a, s); break;
+      case EPI_STORE_GROUPMAX: conv3_launch<PRO_BNRELU, EPI_STORE_GROUPMAX>(a, s); break;
     }
   }
 }

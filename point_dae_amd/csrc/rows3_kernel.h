@@ -1041,7 +1041,6 @@ __global__ __launch_bounds__(512) void wgrad3t_kernel(const rows::WgradArgs g) {
 // accumulators' start value, the group max is a max over a lane's 16 registers and its partner lane (lane ^ 32), and
 // the BatchNorm column statistics meet across the four waves of a column in LDS.
 //   PRO_BNRELU            a := relu(a * scale[k] + shift[k]) on the staged A octet right before it is split
-//   EPI_BIAS              C = acc + bias
 //   EPI_GROUPBIAS_STATS   C = acc + gbias[m / 32]; per-column sum / sum of squares -> stats (atomics per XCD slot, or
 //                         plain per-tile-row partials in deterministic mode)
 //   EPI_STATS             C = acc (+ bias) with the same statistics

@@ -1,6 +1,10 @@
-"""GPU numerics of the hand-written fp32 MFMA GEMM kernels and their fused
-producer / epilogue variants against plain PyTorch fp32 compositions of the
-same ops (tolerance: fp32 GEMM reassociation, 2e-5 of the output scale)."""
+"""GPU numerics of the fused producer / epilogue GEMMs of the patch embedder and
+the set-abstraction MLPs (csrc/gemm.hip: the fp32-input MFMA kernel; csrc/rows3_conv.hip:
+the same contracts on exact-split bf16, the default), of the embedder's memory-bound
+passes and of its group-listed weight gradients (pdae_rows_wgrad_listed), against
+PyTorch compositions of the same ops (tolerance: fp32 GEMM reassociation, 2e-5 of the
+output scale; 5e-5 for weight gradients).  The plain Linear forward / data-gradient /
+weight-gradient products are pinned in test_gpu_rows.py."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -19,59 +23,35 @@ def _close(a, b, tol=2e-5):
     assert err <= tol, err
 
 
-SHAPES = [(4096, 384, 512), (131072, 384, 512), (2944, 1152, 384), (8192, 384, 1536), (1000, 96, 384),
-          (37, 128, 132), (65536, 512, 256), (5248, 96, 384), (300, 1536, 384)]
-
-
-@pytest.mark.parametrize('M,N,K', SHAPES)
-@pytest.mark.parametrize('act', [0, 1, 2])
-def test_linear_forward(M, N, K, act):
-    L = _lib()
-    g = torch.Generator(device='cuda').manual_seed(M + N + K)
-    x = torch.randn(M, K, device='cuda', generator=g)
-    w = torch.randn(N, K, device='cuda', generator=g) / K ** 0.5
-    b = torch.randn(N, device='cuda', generator=g)
-    y = torch.empty(M, N, device='cuda')
-    L.call('pdae_linear_forward', x, M, N, K, x.data_ptr(), w.data_ptr(), b.data_ptr(), act, y.data_ptr())
-    ref = F.linear(x.double(), w.double(), b.double())
-    ref = [ref, F.relu(ref), F.gelu(ref)][act].float()
-    _close(y, ref)
-    L.call('pdae_linear_forward', x, M, N, K, x.data_ptr(), w.data_ptr(), None, 0, y.data_ptr())
-    _close(y, F.linear(x.double(), w.double()).float())
-
-
-@pytest.mark.parametrize('M,N,K', SHAPES)
-def test_linear_backward(M, N, K):
-    L = _lib()
-    g = torch.Generator(device='cuda').manual_seed(7)
-    x = torch.randn(M, K, device='cuda', generator=g)
-    w = torch.randn(N, K, device='cuda', generator=g) / K ** 0.5
-    dy = torch.randn(M, N, device='cuda', generator=g)
-    wt = w.t().contiguous()
-    dx = torch.empty(M, K, device='cuda')
-    L.call('pdae_linear_backward_data', x, M, N, K, dy.data_ptr(), wt.data_ptr(), dx.data_ptr())
-    _close(dx, (dy.double() @ w.double()).float())
-    dw = torch.full((N, K), 7.0, device='cuda')          # must be overwritten, not accumulated
-    db = torch.full((N,), 7.0, device='cuda')
-    L.call('pdae_linear_backward_weight', x, M, N, K, dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr())
-    _close(dw, (dy.double().t() @ x.double()).float(), 5e-5)     # fp32 atomics over M-splits
-    _close(db, dy.double().sum(0).float(), 5e-5)
+def _wgrad_listed(L, M, dy, a_groups, x, b_groups, sc, sh, with_bias):
+    """pdae_rows_wgrad_listed into NaN-filled outputs (a kernel that accumulates fails) -> dW, db."""
+    N, K = dy.shape[1], x.shape[1]
+    ws = torch.full((max(L.rows_wgrad_workspace(M, [N], [K]), 1),), float('nan'), device='cuda')
+    dw = torch.full((N, K), float('nan'), device='cuda')
+    db = torch.full((N,), float('nan'), device='cuda') if with_bias else None
+    L.call('pdae_rows_wgrad_listed', x, M, N, K, L.ptr(dy), L.ptr(a_groups), L.ptr(x), L.ptr(b_groups), L.ptr(sc), L.ptr(sh),
+           L.ptr(dw), L.ptr(db), L.ptr(ws))
+    return dw, db
 
 
 @pytest.mark.parametrize('G,N,K', [(8192, 256, 128), (512, 256, 128), (33, 128, 64), (4096, 384, 512)])
 def test_embed_conv_store_groupmax(G, N, K):
+    """pdae_embed_bnrelu_conv_store_groupmax, first_conv[1..3] + the max of :47: Y and its group max / argmax out of one launch.  Under PDAE_GEMM=f32mfma the
+    four shapes select the 128x128, 256x256 and 128x384 tiles of gemm.hip's launch_nt."""
     L = _lib()
     M = G * 32
     g = torch.Generator(device='cuda').manual_seed(1)
     x = torch.randn(M, K, device='cuda', generator=g)
+    sc = torch.rand(K, device='cuda', generator=g) + 0.5
+    sh = torch.randn(K, device='cuda', generator=g) * 0.3
     w = torch.randn(N, K, device='cuda', generator=g) / K ** 0.5
     b = torch.randn(N, device='cuda', generator=g)
     y = torch.empty(M, N, device='cuda')
     gm = torch.empty(G, N, device='cuda')
     ga = torch.empty(G, N, device='cuda', dtype=torch.uint8)
-    L.call('pdae_embed_conv_store_groupmax', x, M, N, K, x.data_ptr(), w.data_ptr(), b.data_ptr(),
-           y.data_ptr(), gm.data_ptr(), ga.data_ptr())
-    ref = F.linear(x, w, b)
+    L.call('pdae_embed_bnrelu_conv_store_groupmax', x, M, N, K, x.data_ptr(), sc.data_ptr(), sh.data_ptr(),
+           w.data_ptr(), b.data_ptr(), y.data_ptr(), gm.data_ptr(), ga.data_ptr())
+    ref = F.linear(F.relu(x * sc + sh).double(), w.double(), b.double()).float()
     _close(y, ref)
     # max / argmax must be consistent with the Y the kernel itself produced (bit exact)
     mx, am = y.reshape(G, 32, N).max(dim=1)
@@ -125,10 +105,7 @@ def test_embed_bnrelu_conv_groupmax(G, N, K):
     assert (ga.long() == am).float().mean() > 0.999
     # weight gradient with the activation recomputed in the producer
     dy = torch.randn(M, N, device='cuda', generator=g)
-    dw = torch.empty(N, K, device='cuda')
-    db = torch.empty(N, device='cuda')
-    L.call('pdae_bnrelu_linear_backward_weight', x, M, N, K, dy.data_ptr(), x.data_ptr(), sc.data_ptr(),
-           sh.data_ptr(), dw.data_ptr(), db.data_ptr(), None)
+    dw, db = _wgrad_listed(L, M, dy, None, x, None, sc, sh, True)
     _close(dw, (dy.double().t() @ a.double()).float(), 5e-5)
     _close(db, dy.double().sum(0).float(), 5e-5)       # bias gradient from the same kernel
     # group list: only some groups go through the layer, outputs compact in list order
@@ -140,8 +117,7 @@ def test_embed_bnrelu_conv_groupmax(G, N, K):
            w.data_ptr(), b.data_ptr(), gm2.data_ptr(), ga2.data_ptr(), sel.data_ptr())
     assert torch.equal(gm2, gm[sel.long()]) and torch.equal(ga2, ga[sel.long()])
     dyc = torch.randn(Gs * 32, N, device='cuda', generator=g)
-    L.call('pdae_bnrelu_linear_backward_weight', x, Gs * 32, N, K, dyc.data_ptr(), x.data_ptr(), sc.data_ptr(),
-           sh.data_ptr(), dw.data_ptr(), None, sel.data_ptr())
+    dw, _ = _wgrad_listed(L, Gs * 32, dyc, None, x, sel, sc, sh, False)
     a_sel = a.reshape(G, 32, K)[sel.long()].reshape(Gs * 32, K)
     _close(dw, (dyc.double().t() @ a_sel.double()).float(), 5e-5)
 
@@ -294,7 +270,7 @@ def test_conv1_stats_and_bn_finalize(R, C):
 
 def test_listed_group_entries():
     """The group-list entries of the algebraic embedder backward against torch on gathered rows:
-    linear_backward_weight_listed (gathers on either operand; Gram matrix), group_gemm_scatter (gather, per-group
+    rows_wgrad_listed (gathers on either operand; Gram matrix), group_gemm_scatter (gather, per-group
     bias, scatter; untouched rows stay), group_sum_listed, masked_group_sums, and their argument checks."""
     L = _lib()
     g = torch.Generator(device='cuda').manual_seed(5)
@@ -304,15 +280,11 @@ def test_listed_group_entries():
     rows = (lst.long().unsqueeze(1) * 32 + torch.arange(32, device='cuda')).reshape(-1)
     M = rows.numel()
     # Gram matrix of the listed rows
-    gram = torch.full((C, C), float('nan'), device='cuda')
-    L.call('pdae_linear_backward_weight_listed', f, M, C, C, f.data_ptr(), lst.data_ptr(), f.data_ptr(), lst.data_ptr(),
-           gram.data_ptr(), None)
+    gram, _ = _wgrad_listed(L, M, f, lst, f, lst, None, None, False)
     _close(gram, f[rows].double().t() @ f[rows].double(), 2e-5)
     # compact dY against gathered X, with the bias-gradient column sums
     dy = torch.randn(M, K, device='cuda', generator=g)
-    dw, db = torch.empty(K, C, device='cuda'), torch.empty(K, device='cuda')
-    L.call('pdae_linear_backward_weight_listed', f, M, K, C, dy.data_ptr(), None, f.data_ptr(), lst.data_ptr(),
-           dw.data_ptr(), db.data_ptr())
+    dw, db = _wgrad_listed(L, M, dy, None, f, lst, None, None, True)
     _close(dw, dy.double().t() @ f[rows].double(), 2e-5)
     _close(db, dy.double().sum(0), 2e-5)
     # gather -> product -> per-group bias -> scatter
@@ -340,13 +312,11 @@ def test_listed_group_entries():
     L.call('pdae_masked_group_sums', f, lst.numel(), C, hs.data_ptr(), xe.data_ptr(), v.data_ptr(), lst.data_ptr(), dgb.data_ptr())
     assert torch.allclose(dgb[lst.long()], v * hs + 32 * xe, rtol=1e-6, atol=1e-6)
     with pytest.raises(RuntimeError, match='multiple of 32'):
-        L.call('pdae_linear_backward_weight_listed', f, 40, C, C, f.data_ptr(), None, f.data_ptr(), None, gram.data_ptr(), None)
-    with pytest.raises(RuntimeError, match='multiple of 32'):
         L.call('pdae_group_gemm_scatter', f, 40, K, C, f.data_ptr(), None, w.data_ptr(), None, y.data_ptr(), K, lst.data_ptr())
     with pytest.raises(RuntimeError, match='null pointer'):
         L.call('pdae_group_gemm_scatter', f, M, K, C, f.data_ptr(), None, w.data_ptr(), None, y.data_ptr(), K, None)
     with pytest.raises(RuntimeError, match='n_listed <= G'):
-        L.call('pdae_bnrelu_backward_listed', f, 2, C, f.data_ptr(), f.data_ptr(), v.data_ptr(), v.data_ptr(), v.data_ptr(),
+        L.call('pdae_bnrelu_backward_listed_apply', f, 2, C, f.data_ptr(), f.data_ptr(), v.data_ptr(), v.data_ptr(), v.data_ptr(),
                v.data_ptr(), v.data_ptr(), gram.data_ptr(), None, 0, None, 5, lst.data_ptr())
 
 

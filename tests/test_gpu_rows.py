@@ -1,7 +1,9 @@
-"""GPU numerics of the Transformer-block GEMM family (csrc/rows_gemm.hip): every tile shape, both
-weight layouts, the fused epilogues, split-K slabs and the grouped weight-gradient launch, against
-fp64 PyTorch compositions of the same ops (tolerance: fp32 GEMM reassociation, 2e-5 of the output
-scale) -- and bit-identical results run to run (no atomics anywhere)."""
+"""GPU numerics of the row-GEMM family (csrc/rows_gemm.hip), the library's Linear layers -- forward, data
+gradient and weight gradient: every tile shape, both weight layouts, the fused epilogues, split-K slabs
+and the grouped weight-gradient launch, on the Transformer block's shapes and on the wider ones of the
+embedder and the heads (K = 512, N = 512 / K = 256, more tiles than one persistent round), against fp64
+PyTorch compositions of the same ops (tolerance: fp32 GEMM reassociation, 2e-5 of the output scale; 5e-5
+for weight gradients) -- and bit-identical results run to run (no atomics anywhere)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -49,6 +51,44 @@ def test_rows_gemm_store(M, N, K, cfg):
     dy = torch.randn(M, N, device='cuda', generator=g)
     if N % 4 == 0:
         _close(_gemm(L, dy, w, 1, None, 0, None, cfg, 1)[0], dy.double() @ w.double())
+
+
+# one Linear layer at the planned tile shape, beyond SHAPES: a K = 512 reduction, the embedder's N = 512 / K = 256, more
+# tiles than one residency of persistent blocks holds (131072 and 65536 rows), a few rows against N = 1536
+LINEAR_SHAPES = [(4096, 384, 512), (131072, 384, 512), (2944, 1152, 384), (8192, 384, 1536), (1000, 96, 384),
+                 (37, 128, 132), (65536, 512, 256), (5248, 96, 384), (300, 1536, 384)]
+
+
+@pytest.mark.parametrize('M,N,K', LINEAR_SHAPES)
+@pytest.mark.parametrize('act', [0, 1, 2])
+def test_rows_linear_forward(M, N, K, act):
+    """Y = act(X W^T + b), act none / ReLU / GELU (epi 0 / 1 / 2), and without the bias."""
+    L = _lib()
+    g = torch.Generator(device='cuda').manual_seed(M + N + K)
+    x = torch.randn(M, K, device='cuda', generator=g)
+    w = torch.randn(N, K, device='cuda', generator=g) / K ** 0.5
+    b = torch.randn(N, device='cuda', generator=g)
+    z = torch.full((M, N), float('nan'), device='cuda') if act == 2 else None
+    ref = F.linear(x.double(), w.double(), b.double())
+    _close(_gemm(L, x, w, 0, b, act, z, -1, 1)[0], [ref, F.relu(ref), F.gelu(ref)][act])
+    _close(_gemm(L, x, w, 0, None, 0, None, -1, 1)[0], F.linear(x.double(), w.double()))
+
+
+@pytest.mark.parametrize('M,N,K', LINEAR_SHAPES)
+def test_rows_linear_backward(M, N, K):
+    """dX = dY W, and dW, db of ONE layer; their outputs are pre-filled: they must be overwritten, not accumulated into."""
+    L = _lib()
+    g = torch.Generator(device='cuda').manual_seed(7)
+    x = torch.randn(M, K, device='cuda', generator=g)
+    w = torch.randn(N, K, device='cuda', generator=g) / K ** 0.5
+    dy = torch.randn(M, N, device='cuda', generator=g)
+    _close(_gemm(L, dy, w, 1, None, 0, None, -1, 1)[0], dy.double() @ w.double())
+    dw = torch.full((N, K), 7.0, device='cuda')
+    db = torch.full((N,), 7.0, device='cuda')
+    ws = torch.full((max(L.rows_wgrad_workspace(M, [N], [K]), 1),), float('nan'), device='cuda')
+    L.rows_wgrad(dy, M, [dy], [x], [dw], [db], ws)
+    _close(dw, dy.double().t() @ x.double(), 5e-5)
+    _close(db, dy.double().sum(0), 5e-5)
 
 
 @pytest.mark.parametrize('M,N,K', [(2944, 1536, 384), (8192, 1536, 384), (333, 1536, 384), (2944, 128, 4)])

@@ -1,9 +1,9 @@
-"""GEMM micro-benchmark on the Transformer-block shapes of the step: hand-written fp32 MFMA kernels
-(C ABI) vs torch.mm (hipBLASLt).  M = 128 * T_vis rows in the encoder, 8192 in the decoder."""
+"""GEMM micro-benchmark on the Transformer-block shapes of the step: the hand-written row GEMMs
+(point_dae_amd/rows.py, in the arithmetic PDAE_GEMM selects) vs torch.mm (hipBLASLt).  M = 128 * T_vis rows in the encoder, 8192 in the decoder."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from point_dae_amd import _lib
+from point_dae_amd import rows
 from point_dae_amd.graph_step import use_created_stream
 
 use_created_stream()
@@ -25,15 +25,13 @@ tot = {}
 for M in Ms:
     for name, N, K in layers:
         x = torch.randn(M, K, device='cuda'); w = torch.randn(N, K, device='cuda') * 0.05; b = torch.randn(N, device='cuda')
-        y = torch.empty(M, N, device='cuda')
-        dy = torch.randn(M, N, device='cuda'); wt = w.t().contiguous(); dx = torch.empty(M, K, device='cuda')
-        dw = torch.empty(N, K, device='cuda'); db = torch.empty(N, device='cuda')
+        dy = torch.randn(M, N, device='cuda')
         fl = 2.0 * M * N * K / 1e6     # MFLOP -> /us = TFLOP/s
-        f1 = lambda: _lib.call('pdae_linear_forward', x, M, N, K, x.data_ptr(), w.data_ptr(), b.data_ptr(), 0, y.data_ptr())
+        f1 = lambda: rows.rows_gemm(x, w, False, b)
         f2 = lambda: torch.mm(x, w.t())
-        g1 = lambda: _lib.call('pdae_linear_backward_data', x, M, N, K, dy.data_ptr(), wt.data_ptr(), dx.data_ptr())
+        g1 = lambda: rows.rows_gemm(dy, w, True)
         g2 = lambda: torch.mm(dy, w)
-        h1 = lambda: _lib.call('pdae_linear_backward_weight', x, M, N, K, dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr())
+        h1 = lambda: rows.rows_wgrad([dy], [x], [True])
         h2 = lambda: torch.mm(dy.t(), x)
         t = [timeit(f) for f in (f1, f2, g1, g2, h1, h2)]
         for k, v in zip(('fwd_mine', 'fwd_lib', 'dx_mine', 'dx_lib', 'dw_mine', 'dw_lib'), t):
