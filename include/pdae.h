@@ -1041,6 +1041,38 @@ int pdae_svm_ovo_predict(int m, int n, int ld, int K, int nC, const float* Gte, 
                          pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Task-affinity protocol (csrc/affinity.hip; tools/runner_finetune.py:1198-1269 of the reference trains
+ * nn.Linear(feat_dim, num_class) on the frozen encoder's features and reports the test cross-entropy and accuracy).
+ *   linear_probe_train  trains W (K, D) and b (K) fp32 IN PLACE from their initial values on X (n x ld fp32, ld >= D)
+ *                       and labels (n, 0 .. K - 1): `epochs` epochs of floor(n / PDAE_PROBE_BATCH) batches; step t
+ *                       (global, from 1, running on across the epochs) takes the rows
+ *                       perm[e][64 i .. 64 i + 63] (perm: device, epochs x n, every row a permutation of 0 .. n - 1; X is
+ *                       gathered through it, never copied), logits = x W^T + b, loss = the mean cross-entropy of
+ *                       the 64 rows, then torch.optim.AdamW's update in pdae_adamw_step's order with the decay on W and
+ *                       b alike.  lr: HOST, `epochs` doubles, the learning rate of each epoch; the bias corrections
+ *                       1 - beta^t are formed in fp64 on the host.  ONE launch per step (plus a prologue and a fill) on
+ *                       `stream`, no host synchronisation and no wait between workgroups; every sum has a fixed order
+ *                       and there are no atomics: two calls give the same bits.  workspace: linear_probe_workspace(D, K)
+ *                       floats (the moments, the double-buffered partial logits and bias).  floor(n / 64) == 0 or
+ *                       epochs == 0: nothing is launched, W and b are untouched.
+ *                       K < 2, D < 1, ld < D, n < 0: PDAE_ERR_BAD_ARG; K > PDAE_PROBE_MAX_CLASSES: PDAE_ERR_UNSUPPORTED;
+ *                       both before anything is launched (linear_probe_supported answers the same on the host).
+ *   linear_probe_eval   on X (m x ld), labels (m): row_loss (m) fp32 = the rows' cross-entropies, row_pred (m) int32 =
+ *                       argmax of the logits, ties to the lowest class; *loss_sum fp64 = the sum of row_loss and
+ *                       *correct int32 = the rows with row_pred == label, both added in a fixed order;
+ *                       logits (m, K), nullable.  Any m >= 1.                                                             */
+#define PDAE_PROBE_MAX_CLASSES 64
+#define PDAE_PROBE_BATCH 64
+int pdae_linear_probe_supported(int n, int D, int ld, int K);
+long long pdae_linear_probe_workspace(int D, int K);
+int pdae_linear_probe_train(int n, int D, int ld, int K, int epochs, const float* X, const int32_t* labels,
+                            const int32_t* perm, float* W, float* b, const double* lr /*host*/, double beta1, double beta2,
+                            double eps, double weight_decay, float* workspace, pdae_stream_t stream);
+int pdae_linear_probe_eval(int m, int D, int ld, int K, const float* X, const int32_t* labels, const float* W,
+                           const float* b, float* row_loss, int32_t* row_pred, float* logits /*nullable*/,
+                           double* loss_sum, int32_t* correct, pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Measurement aids: box calibration for bench.py (csrc/calib.hip).  They replace nothing of the reference; the training
  * step never calls them.  MI355X boxes differ by +-4 % on the step and by up to 12 % on matrix loops (the clock a device
  * holds under load), so a bench line carries the rates of two kernels of known work next to its headline.

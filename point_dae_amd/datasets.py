@@ -502,6 +502,76 @@ class ShapeNet:
             yield self.ids[int(sel[0])][0], i, corrupted, clean
 
 
+def taxonomy_ranks(data_path):
+    """{taxonomy id: label} of a listed set: the rank of the id among the sorted distinct taxonomy ids of
+    `<data_path>/train.txt` and `<data_path>/test.txt` together (whichever exist)."""
+    ids = set()
+    for subset in ('train', 'test'):
+        path = os.path.join(str(data_path), '%s.txt' % subset)
+        if os.path.exists(path):
+            with open(path) as f:
+                ids.update(line.split('-')[0] for line in f.read().split())
+    return {tax: rank for rank, tax in enumerate(sorted(ids))}
+
+
+@DATASETS.register_module()
+class ShapeNetClass(ShapeNet):
+    """ShapeNet with class labels, for the task-affinity protocol (datasets/ShapeNet55Dataset.py ShapeNetClass of the
+    reference): yields (taxonomy, model_id, (points (B, npoints, 3), labels (B,))) in list order.  The points are the
+    `corrupted` output of ShapeNet.batch -- augment_data, corrupt_data on the whole cloud, random_sample(npoints) --, first
+    three columns.  The `train` subset drops a short last batch (tools/builder.py: drop_last), the others keep it.
+
+    Labels of a listed set: the rank of a file's taxonomy id among the sorted distinct taxonomy ids of train.txt and
+    test.txt together (taxonomy_ranks).  The reference maps its 55 synset ids through a table in ascending order, so the
+    two agree whenever all 55 classes are present in the lists; with classes missing the ranks close the gaps.
+    Without files, labelled synthetic clouds stand in (synthetic.labelled_clouds; `count` clouds of `classes` classes), as
+    for datasets.ModelNet.
+
+    A corrupt_type item that ShapeNet.batch leaves to the model's forward (dropout_patch_pointmae, Drop-Patch,
+    dropout_global*) is refused: nothing would apply it in this protocol."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        for item in self.corrupt_type:
+            if (item in _PASS and item != 'clean') or 'dropout_global' in item:
+                raise NotImplementedError('ShapeNetClass: corruption %r is applied in the model\'s forward by the pretraining '
+                                          'models; nothing applies it in this protocol' % item)
+        self.bs = config.get('bs', 64)
+        self.count = config.get('count', 256)
+        self.classes = int(config.get('classes', 3))
+        self.labels = None
+
+    def _materialise(self):
+        listed = self.pc_path and self.data_path and os.path.exists(os.path.join(str(self.data_path), '%s.txt' % self.subset))
+        if listed:
+            clouds, self.ids = load_npy_clouds(self.pc_path, self.data_path, self.subset)
+            clouds = clouds[:, :, :3]
+            ranks = taxonomy_ranks(self.data_path)
+            labels = np.array([ranks[tax] for tax, _ in self.ids], np.int64)
+        else:
+            seed = self.seed + (1000 if self.subset == 'train' else 2000)
+            clouds, labels = labelled_clouds(self.count, max(self.dense, 2 * self.npoints), seed=seed, classes=self.classes)
+            self.ids = [('synthetic', str(i)) for i in range(self.count)]
+        self.count = clouds.shape[0]
+        self._clouds = torch.from_numpy(np.ascontiguousarray(clouds)).to(self.device)
+        self.labels = torch.from_numpy(labels).to(self.device)
+        self.gen = torch.Generator(device=self._clouds.device)
+        self.gen.manual_seed(self.seed)
+        self.listed = bool(listed)
+        self.steps = self.count // self.bs if self.subset == 'train' else -(-self.count // self.bs)
+
+    def __iter__(self):
+        if self._clouds is None:
+            self._materialise()
+        dev = self._clouds.device
+        end = self.steps * self.bs if self.subset == 'train' else self.count
+        for i in range(0, end, self.bs):
+            sel = np.arange(i, min(i + self.bs, end))
+            corrupted, _ = self.batch(_dev(sel, dev))
+            tax, model_id = self.ids[i]
+            yield tax, model_id, (corrupted[:, :, :3], self.labels[i:i + len(sel)])
+
+
 @DATASETS.register_module()
 class ModelNet:
     """Labelled clouds for the SVM probe (datasets/ModelNetDataset.py of the reference yields

@@ -1,7 +1,7 @@
 """Entry point: `python -m point_dae_amd.main --config cfgs/X.yaml [--launcher pytorch]`
 (main.py:16-111 of the reference): pretraining, or with --finetune_model / --scratch_model the
 classification fine-tuning runner (--so3_rotation: its rotation-robustness protocol; --svm_classification: the linear-SVM
-evaluation of the frozen encoder)."""
+evaluation of the frozen encoder; --task_affinity: the linear probe whose test loss ranks corruptions)."""
 import torch
 
 from . import dist_utils, parser
@@ -19,6 +19,9 @@ def main(argv=None):
         # the reference runs this protocol in ONE process under DataParallel (rerun.sh); its distributed branch would fit
         # every rank's SVMs on that rank's shard of the features
         raise ValueError('--svm_classification runs in one process: --launcher none')
+    if args.task_affinity and args.launcher != 'none':
+        # (the same: every rank would train its probe on its own shard of the features)
+        raise ValueError('--task_affinity runs in one process: --launcher none')
     if args.launcher == 'none':
         args.distributed = False
         args.world_size = 1
@@ -43,6 +46,8 @@ def main(argv=None):
     set_random_seed(args.seed + args.local_rank, deterministic=args.deterministic)   # main.py:78-81
     if finetune and args.svm_classification:
         runner_finetune.svm_classification(args, config)                   # main.py:102-103
+    elif finetune and args.task_affinity:
+        runner_finetune.task_affinity(args, config)                        # main.py:104-105
     elif finetune and args.so3_rotation:
         runner_finetune.run_net_rotation(args, config)                     # main.py:106-107
     elif finetune:

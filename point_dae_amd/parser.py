@@ -28,6 +28,8 @@ def get_args(argv=None):
                    help='rotation-robustness fine-tuning: y-axis train rotation, ten-pass rotated validation')
     p.add_argument('--svm_classification', action='store_true', default=False,
                    help='linear-SVM evaluation of the frozen encoder: SVC(kernel=linear) for C = 1e-3 .. 1e2')
+    p.add_argument('--task_affinity', action='store_true', default=False,
+                   help='evaluate task affinity with pre-trained encoder.')
     # synthetic-data controls (no dataset ships with this repo)
     p.add_argument('--max_epoch', type=int, default=-1, help='override config.max_epoch')
     p.add_argument('--steps_per_epoch', type=int, default=None,

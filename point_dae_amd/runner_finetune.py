@@ -11,6 +11,9 @@ the resample (data_transforms.resample_transformed: one launch into the graphed 
 
 svm_classification (:902-1049, main.py --svm_classification) trains nothing: one eval pass of the frozen encoder over the
 train and the val loader, then the six linear SVMs of svm_ops on the features, which never leave the device.
+
+task_affinity (:1052-1269, main.py --task_affinity) makes the same two passes, then trains the linear probe of
+affinity_ops on the train features and reports its accuracy and mean cross-entropy on the test features.
 """
 import time
 
@@ -241,12 +244,10 @@ def extract_svm_features(base_model, loader, npoints):
     return torch.cat(feats, 0), torch.cat(labels, 0)
 
 
-def svm_classification(args, config, log=print):
-    """runner_finetune.py:902-1049: the features of the train loader (its short last batch dropped), then of the val
-    loader, from the frozen model in eval mode; SVC(C=c, kernel='linear') for c = 10**i, i in range(-3, 3) (svm_ops:
-    the gfx950 solver, or PDAE_SVM=sklearn); the reference's lines -- the running best per c, then its
-    '[Validation] EPOCH' line, whose epoch field is the last c -- -> Acc_Metric(best test accuracy, a fraction)."""
-    from . import svm_ops
+def _frozen_features(args, config, log):
+    """The part svm_classification and task_affinity share: one process, the train and val loaders, the model frozen in
+    eval mode, extract_svm_features over both -> (train features, labels, test features, labels) on the device; the two
+    feature shapes are logged as the reference prints them."""
     rank, world = dist_utils.get_dist_info()
     device = torch.device('cuda', torch.cuda.current_device())
     from .graph_step import use_created_stream
@@ -267,6 +268,16 @@ def svm_classification(args, config, log=print):
     log(str(tuple(feats_train.shape)))
     feats_test, labels_test = extract_svm_features(base_model, test_loader, config.npoints)
     log(str(tuple(feats_test.shape)))
+    return feats_train, labels_train, feats_test, labels_test
+
+
+def svm_classification(args, config, log=print):
+    """runner_finetune.py:902-1049: the features of the train loader (its short last batch dropped), then of the val
+    loader, from the frozen model in eval mode; SVC(C=c, kernel='linear') for c = 10**i, i in range(-3, 3) (svm_ops:
+    the gfx950 solver, or PDAE_SVM=sklearn); the reference's lines -- the running best per c, then its
+    '[Validation] EPOCH' line, whose epoch field is the last c -- -> Acc_Metric(best test accuracy, a fraction)."""
+    from . import svm_ops
+    feats_train, labels_train, feats_test, labels_test = _frozen_features(args, config, log)
     log('SVM backend: %s' % svm_ops.backend())
     max_acc, c = 0, None
     for c, acc in zip(svm_ops.SVM_CS, svm_ops.accuracies(feats_train, labels_train, feats_test, labels_test)):
@@ -275,3 +286,16 @@ def svm_classification(args, config, log=print):
         log('%s %s' % (c, max_acc))
     log('[Validation] EPOCH: %d  acc = %.4f' % (c, max_acc))
     return Acc_Metric(max_acc)
+
+
+def task_affinity(args, config, log=print):
+    """runner_finetune.py:1052-1269: the features of the train and the val loader from the frozen model, as for
+    svm_classification; then the linear probe of affinity_ops (300 epochs of AdamW under the cosine schedule: one
+    launch per step on csrc/affinity.hip, or PDAE_AFFINITY=torch) and the reference's line, which
+    parse_test_res.py --taskaffinity reads -> (accuracy as a fraction, mean test cross-entropy)."""
+    from . import affinity_ops
+    feats_train, labels_train, feats_test, labels_test = _frozen_features(args, config, log)
+    log('Affinity backend: %s' % affinity_ops.backend())
+    acc, loss = affinity_ops.task_affinity_loss(feats_train, labels_train, feats_test, labels_test)
+    log('[Validation] Acc: %.4f  loss = %.4f' % (acc, loss))
+    return acc, loss
