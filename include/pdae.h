@@ -1073,7 +1073,34 @@ int pdae_linear_probe_eval(int m, int D, int ld, int K, const float* X, const in
                            double* loss_sum, int32_t* correct, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
- * Measurement aids: box calibration for bench.py (csrc/calib.hip).  They replace nothing of the reference; the training
+ * Voted evaluation (csrc/vote.hip; tools/runner_finetune.py:835-899 test_vote / :568-632 validate_vote of the reference:
+ * per test batch `times` subsets of the FPS order, each through test_transforms and the model, the mean of the logits,
+ * its argmax).
+ *   vote_resample  pdae_resample_affine for all v votes of a batch in ONE launch:
+ *                    out[k,b,n,j] = sum_i raw[b, fps_idx[b, choice[k,n]], i] * A[k,b,i,j] + t[k,b,j]      i, j in 0..2
+ *                  raw (b,p,c) with c >= 3, fps_idx (b,point_all), choice (v,npoints): one subset per vote, shared by the
+ *                  batch; A (v,b,3,3) and t (v,b,3) each nullable; out (v,b,npoints,3).  The arithmetic is
+ *                  pdae_resample_affine's (the sum i = 0, 1, 2, then + t, every operation rounded; no map: the
+ *                  coordinates are moved bit for bit; an index outside its array is not followed, that point is written
+ *                  as NaN): the result equals v calls of it bit for bit.  Non-positive sizes, c < 3,
+ *                  npoints > point_all, a null required pointer: PDAE_ERR_BAD_ARG; more blocks than one launch takes:
+ *                  PDAE_ERR_UNSUPPORTED; both before anything is launched.
+ *   vote_reduce    logits (v,b,k) fp32, labels (b) int64: per row the fp32 sum over the votes in the order 0 .. v-1,
+ *                  divided by (float)v -> mean_out (b,k), nullable; pred_out (b) int64 = its argmax, ties to the lowest
+ *                  class, -1 when a logit of the row is NaN; *correct (ONE int32) += the rows with pred == label (a row
+ *                  of -1 and a label outside 0 .. k-1 never count).  One workgroup, a fixed order, no atomics: the count
+ *                  is added with a plain load and store, so launches that share a counter must share a stream.  Any
+ *                  b >= 1, v >= 1; v, b, k < 1 or a null required pointer: PDAE_ERR_BAD_ARG; k > PDAE_VOTE_MAX_CLASSES:
+ *                  PDAE_ERR_UNSUPPORTED.                                                                                 */
+#define PDAE_VOTE_MAX_CLASSES 64
+int pdae_vote_resample(int v, int b, int p, int c, int point_all, int npoints, const float* raw, const int32_t* fps_idx,
+                       const int32_t* choice, const float* A /*nullable*/, const float* t /*nullable*/, float* out,
+                       pdae_stream_t stream);
+int pdae_vote_reduce(int v, int b, int k, const float* logits, const int64_t* labels, float* mean_out /*nullable*/,
+                     int64_t* pred_out, int32_t* correct, pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Measurement aids: box calibration for bench.py (csrc/calib.hip). They replace nothing of the reference; the training
  * step never calls them.  MI355X boxes differ by +-4 % on the step and by up to 12 % on matrix loops (the clock a device
  * holds under load), so a bench line carries the rates of two kernels of known work next to its headline.
  *   calib_mfma_bf16  `blocks` work-groups of 4 waves (one per SIMD) each issue iters x 32 v_mfma_f32_32x32x16_bf16 on

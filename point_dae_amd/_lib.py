@@ -143,6 +143,8 @@ _SIGNATURES = {
     "pdae_linear_probe_train": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, _vp, _vp],
     "pdae_linear_probe_eval": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_vote_resample": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_vote_reduce": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_calib_mfma_bf16": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_calib_copy": [ctypes.c_longlong, _vp, _vp, _vp],
 }

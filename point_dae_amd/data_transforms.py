@@ -49,7 +49,8 @@ class PointcloudScaleAndTranslate(object):
     def __init__(self, scale_low=2. / 3., scale_high=3. / 2., translate_range=0.2):
         self.scale_low, self.scale_high, self.translate_range = scale_low, scale_high, translate_range
 
-    def draw(self, B, device=None):
+    def draw_host(self, B):
+        """The draws alone -> host arrays A (B,3,3), t (B,3) (vote_ops.draw_votes ships the maps of all votes at once)."""
         A = np.zeros((B, 3, 3), np.float32)
         t = np.empty((B, 3), np.float32)
         for i in range(B):
@@ -57,7 +58,10 @@ class PointcloudScaleAndTranslate(object):
             xyz2 = np.random.uniform(low=-self.translate_range, high=self.translate_range, size=[3])
             A[i, [0, 1, 2], [0, 1, 2]] = xyz1.astype(np.float32)
             t[i] = xyz2.astype(np.float32)
-        return _ship(A, t, device)
+        return A, t
+
+    def draw(self, B, device=None):
+        return _ship(*self.draw_host(B), device)
 
 
 def resample_affine(raw, fps_idx, choice, A=None, t=None, out=None):

@@ -1,7 +1,9 @@
 """Entry point: `python -m point_dae_amd.main --config cfgs/X.yaml [--launcher pytorch]`
 (main.py:16-111 of the reference): pretraining, or with --finetune_model / --scratch_model the
 classification fine-tuning runner (--so3_rotation: its rotation-robustness protocol; --svm_classification: the linear-SVM
-evaluation of the frozen encoder; --task_affinity: the linear probe whose test loss ranks corruptions)."""
+evaluation of the frozen encoder; --task_affinity: the linear probe whose test loss ranks corruptions; --vote: a ten-vote
+validation behind a high plain one), or with --test --ckpts the evaluation of a fine-tuned checkpoint: the plain accuracy,
+then --vote_rounds rounds of ten-vote evaluation."""
 import torch
 
 from . import dist_utils, parser
@@ -22,6 +24,8 @@ def main(argv=None):
     if args.task_affinity and args.launcher != 'none':
         # (the same: every rank would train its probe on its own shard of the features)
         raise ValueError('--task_affinity runs in one process: --launcher none')
+    if args.test and args.launcher != 'none':
+        raise NotImplementedError('--test runs in one process: --launcher none')   # runner_finetune.py:697-699
     if args.launcher == 'none':
         args.distributed = False
         args.world_size = 1
@@ -39,12 +43,14 @@ def main(argv=None):
     if args.max_epoch != -1:
         config.max_epoch = args.max_epoch
     finetune = args.finetune_model or args.scratch_model
-    if not finetune and len(config.model['corrupt_type']) == 0:          # main.py:51-55 (pretraining configs only)
+    if not finetune and not args.test and len(config.model['corrupt_type']) == 0:   # main.py:51-55 (pretraining configs only)
         config.model['corrupt_type'] = config.dataset['train']['others']['corrupt_type']
     assert config.total_bs % args.world_size == 0
     config.dataset.train.others.bs = config.total_bs // args.world_size
     set_random_seed(args.seed + args.local_rank, deterministic=args.deterministic)   # main.py:78-81
-    if finetune and args.svm_classification:
+    if args.test:
+        runner_finetune.test_net(args, config)                             # main.py:94-95
+    elif finetune and args.svm_classification:
         runner_finetune.svm_classification(args, config)                   # main.py:102-103
     elif finetune and args.task_affinity:
         runner_finetune.task_affinity(args, config)                        # main.py:104-105

@@ -20,7 +20,9 @@ def get_args(argv=None):
     p.add_argument('--start_ckpts', type=str, default=None, help='reload used ckpt path')
     p.add_argument('--ckpts', type=str, default=None)
     p.add_argument('--val_freq', type=int, default=1, help='test freq')
+    p.add_argument('--vote', action='store_true', default=False, help='vote acc')
     p.add_argument('--resume', action='store_true', default=False)
+    p.add_argument('--test', action='store_true', default=False, help='test mode for certain ckpt')
     p.add_argument('--total_bs', type=int, default=-1)
     p.add_argument('--finetune_model', action='store_true', default=False, help='finetune modelnet with pretrained weight')
     p.add_argument('--scratch_model', action='store_true', default=False, help='training modelnet from scratch')
@@ -36,7 +38,15 @@ def get_args(argv=None):
                    help='batches per epoch; default for a listed .npy set: the reference\'s DataLoader length -- '
                         'floor(ceil(N / world) / bs) for the training subset (drop_last, tools/builder.py:21,28), ceil '
                         'otherwise; 50 for the synthetic set')
+    p.add_argument('--vote_rounds', type=int, default=299,
+                   help='--test: rounds of ten-vote evaluation (the reference hard-codes range(1, 300))')
     args = p.parse_args(argv)
+    if args.test and args.resume:
+        raise ValueError('--test and --resume cannot be both activate')
+    if args.test and args.ckpts is None:
+        raise ValueError('ckpts shouldnt be None while test mode')
+    if args.vote_rounds < 0:
+        raise ValueError('--vote_rounds must not be negative')
     if args.resume and args.start_ckpts is not None:
         raise ValueError('--resume and --start_ckpts cannot be both activate')
     if args.finetune_model and args.scratch_model:
@@ -45,6 +55,8 @@ def get_args(argv=None):
         os.environ['LOCAL_RANK'] = str(args.local_rank)
     else:
         args.local_rank = int(os.environ['LOCAL_RANK'])
+    if args.test:
+        args.exp_name = 'test_' + args.exp_name
     stem = Path(args.config).stem + args.model_name
     args.experiment_path = os.path.join('./' + args.root_folder, stem, Path(args.config).parent.stem, args.exp_name)
     args.tfboard_path = os.path.join('./' + args.root_folder, stem, Path(args.config).parent.stem, 'TFBoard', args.exp_name)

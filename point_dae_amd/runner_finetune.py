@@ -14,6 +14,11 @@ train and the val loader, then the six linear SVMs of svm_ops on the features, w
 
 task_affinity (:1052-1269, main.py --task_affinity) makes the same two passes, then trains the linear probe of
 affinity_ops on the train features and reports its accuracy and mean cross-entropy on the test features.
+
+test_net / test_vote / validate_vote (:686-748, :835-899, :568-632; main.py --test, --vote) evaluate a fine-tuned
+checkpoint by voting: per test cloud ten subsets of its FPS order, each through test_transforms and the model, the mean of
+the logits.  vote_pass runs one such pass on vote_ops (csrc/vote.hip); FPS is kept per test batch across passes, the hits
+are counted on the device and test_net reads its rounds' counters once.
 """
 import time
 
@@ -30,6 +35,7 @@ from .registry import DATASETS
 from .svm_probe import Acc_Metric
 
 POINT_ALL = {1024: 1200, 2048: 2400, 4096: 4800, 8192: 8192}      # runner_finetune.py:160-171
+VOTE_POINT_ALL = {1024: 1200, 4096: 4800, 8192: 8192}             # runner_finetune.py:846-853 (voting: no 2048 row)
 
 
 def set_bn_eval(m):
@@ -122,6 +128,119 @@ def validate_rotation(base_model, test_loader, epoch, config, args=None, log=pri
     return Acc_Metric(float(acc))
 
 
+def vote_point_all(npoints, cloud_size):
+    """runner_finetune.py:846-856: the voting table's FPS size for npoints, capped at the cloud's size."""
+    if npoints not in VOTE_POINT_ALL:
+        raise NotImplementedError('voting with npoints %d (the reference votes at 1024, 4096 and 8192)' % npoints)
+    return min(VOTE_POINT_ALL[npoints], cloud_size)
+
+
+def vote_pass(base_model, test_loader, config, times=10, fps_cache=None, correct=None):
+    """One voted pass over the test loader (runner_finetune.py:843-880) on vote_ops: per batch FPS to point_all points
+    -- taken from fps_cache[batch] when the list holds it, appended to the list otherwise: the test subset is not
+    shuffled and FPS draws nothing, so a batch's FPS order is the same on every pass --, the host draws of the `times`
+    votes (vote_ops.draw_votes), vote_ops.vote_batch.  correct: one int32 device counter that receives the hits (a fresh
+    one by default).  Nothing is read back.  -> (pred (n,), label (n,), mean logits (n, K), correct)."""
+    from . import vote_ops
+    from .data_transforms import PointcloudScaleAndTranslate
+    test_transforms = PointcloudScaleAndTranslate()                       # runner_finetune.py:53-59
+    preds, labels, means = [], [], []
+    for i, (_, _, data) in enumerate(test_loader):
+        raw, label = data[0].cuda().contiguous(), data[1].cuda().view(-1).long()
+        if correct is None:
+            correct = torch.zeros(1, dtype=torch.int32, device=raw.device)
+        B, P, C = raw.shape
+        point_all = vote_point_all(config.npoints, P)
+        if fps_cache is not None and i < len(fps_cache):
+            fps_idx = fps_cache[i]
+        else:
+            fps_idx = furthest_point_sample(raw if C == 3 else raw[:, :, :3].contiguous(), point_all)
+            if fps_cache is not None:
+                fps_cache.append(fps_idx)
+        draws = vote_ops.draw_votes(B, point_all, config.npoints, times, test_transforms, device=raw.device)
+        pred, mean = vote_ops.vote_batch(base_model, raw, fps_idx, label, draws, correct)
+        preds.append(pred)
+        labels.append(label)
+        means.append(mean)
+    return torch.cat(preds), torch.cat(labels), torch.cat(means), correct
+
+
+def fps_cacheable(test_loader):
+    """Whether a loader yields the same clouds on every pass, so that a batch's FPS order may be kept: the ModelNet set
+    with no augmentation but 'norm' (every other item draws per pass)."""
+    aug = getattr(test_loader, 'aug_type', None)
+    return aug is not None and all(item == 'norm' for item in aug)
+
+
+def _percent(correct, total):
+    """The reference's (pred == label).sum() / float(n) * 100. -- a division and a product of fp32 tensors."""
+    return float(np.float32(correct) / np.float32(total) * np.float32(100.))
+
+
+@torch.no_grad()
+def test_vote(base_model, test_loader, config, args=None, times=10, fps_cache=None):
+    """runner_finetune.py:835-899: the accuracy in percent of the mean logits of `times` votes per test cloud.
+    fps_cache: a list of per-batch fps_idx tensors; the first pass fills it, later passes reuse it."""
+    base_model.eval()
+    pred, label, _, correct = vote_pass(base_model, test_loader, config, times, fps_cache)
+    if args is not None and getattr(args, 'distributed', False):
+        pred, label = dist_utils.gather_tensor(pred, args), dist_utils.gather_tensor(label, args)
+        return _percent((pred == label).sum().item(), label.numel())
+    return _percent(correct.item(), label.numel())
+
+
+@torch.no_grad()
+def validate_vote(base_model, test_loader, epoch, config, args=None, log=print, times=10, fps_cache=None):
+    """runner_finetune.py:568-632: test_vote inside run_net (--vote), gathered across the ranks as validate is."""
+    log('[VALIDATION_VOTE] epoch %d' % epoch)
+    acc = test_vote(base_model, test_loader, config, args, times, fps_cache)
+    log('[Validation_vote] EPOCH: %d  acc_vote = %.4f' % (epoch, acc))
+    return Acc_Metric(acc)
+
+
+@torch.no_grad()
+def test_net(args, config, log=print):
+    """runner_finetune.py:686-748 (main.py --test): the test loader, the model with builder.load_model(args.ckpts) in
+    eval mode; '[TEST] acc' of the plain pass (FPS to npoints, argmax), then args.vote_rounds (the reference: 299) rounds
+    of ten-vote evaluation and the best of them.  Under PDAE_VOTE=hip every round adds its hits to a device counter of
+    its own, FPS runs once per batch for the whole test, and the host reads all counters once behind the last round --
+    the rounds' lines are printed then; PDAE_VOTE=torch reads and prints round by round.  -> the best accuracy."""
+    from . import vote_ops
+    if getattr(args, 'distributed', False) or getattr(args, 'launcher', 'none') != 'none':
+        raise NotImplementedError('--test runs in one process (the reference raises for --launcher pytorch too)')
+    device = torch.device('cuda', torch.cuda.current_device())
+    log('Tester start ... ')
+    test_loader = _loader(config.dataset.test, device, args.seed, 0, 1, config.total_bs)
+    base_model = builder.model_builder(config.model)
+    builder.load_model(base_model, args.ckpts)
+    base_model = base_model.to(device).eval()
+    pred, label = _predict(base_model, test_loader, config, args)
+    total = label.numel()
+    log('[TEST] acc = %.4f' % _percent((pred == label).sum().item(), total))
+    log('[TEST_VOTE]')
+    rounds = int(getattr(args, 'vote_rounds', 299))
+    fused = vote_ops.backend() == 'hip'
+    log('Vote backend: %s' % vote_ops.backend())
+    fps_cache = [] if fused and fps_cacheable(test_loader) else None
+    counters = torch.zeros(max(rounds, 1), dtype=torch.int32, device=device)
+    accs = []
+    for r in range(rounds):
+        vote_pass(base_model, test_loader, config, 10, fps_cache, counters[r:r + 1])
+        if not fused:
+            accs.append(_percent(counters[r].item(), total))
+            log('[TEST_VOTE_time %d]  acc = %.4f, best acc = %.4f' % (r + 1, accs[-1], max(accs)))
+    acc = 0.
+    if fused:
+        for r, hits in enumerate(counters[:rounds].tolist()):           # the test's one read-back
+            this_acc = _percent(hits, total)
+            acc = max(acc, this_acc)
+            log('[TEST_VOTE_time %d]  acc = %.4f, best acc = %.4f' % (r + 1, this_acc, acc))
+    elif accs:
+        acc = max(accs)
+    log('[TEST_VOTE] acc = %.4f' % acc)
+    return acc
+
+
 def _loader(node, device, seed, rank, world, bs, steps_per_epoch=None):
     c = dict(node._base_)
     c.update(dict(node.others))
@@ -183,6 +302,9 @@ def _run(args, config, log, log_every, train_transform=None, validate_fn=validat
     if int(config.get('step_per_update', 1)) != 1:
         raise NotImplementedError('runner_finetune: step_per_update > 1 (gradient accumulation) is not supported')
     best_metrics, metrics = Acc_Metric(best_metric), Acc_Metric(0.)
+    # --vote: one voted validation behind a plain one that is high enough; the test batches' FPS orders are kept across them
+    vote, best_metrics_vote = bool(getattr(args, 'vote', False)), Acc_Metric(0.)
+    vote_fps = [] if vote and fps_cacheable(test_loader) else None
     # the step is replayed as a hipGraph (graph_step.GraphedClassifierStep)
     from .graph_step import GraphedClassifierStep
     if train_transform is not None:
@@ -224,9 +346,15 @@ def _run(args, config, log, log_every, train_transform=None, validate_fn=validat
                 item.step(epoch)
         if epoch % max(int(getattr(args, 'val_freq', 1)), 1) == 0:
             metrics = validate_fn(base_model, test_loader, epoch, config, args, log=log)
-            if metrics.better_than(best_metrics):
+            better = metrics.better_than(best_metrics)
+            if better:
                 best_metrics = metrics
                 builder.save_checkpoint(model, optimizer, epoch, metrics, best_metrics, 'ckpt-best', args)
+            if vote and (metrics.acc > 92.1 or (better and metrics.acc > 91)):          # runner_finetune.py:254-262
+                metrics_vote = validate_vote(base_model, test_loader, epoch, config, args, log=log, fps_cache=vote_fps)
+                if metrics_vote.better_than(best_metrics_vote):
+                    best_metrics_vote = metrics_vote
+                    builder.save_checkpoint(model, optimizer, epoch, metrics, best_metrics_vote, 'ckpt-best_vote', args)
         builder.save_checkpoint(model, optimizer, epoch, metrics, best_metrics, 'ckpt-last', args)
     return model
 
