@@ -1100,6 +1100,28 @@ int pdae_vote_reduce(int v, int b, int k, const float* logits, const int64_t* la
                      int64_t* pred_out, int32_t* correct, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The training batch of a few-shot episode (csrc/fewshot.hip).
+ * Replaces, per batch row, ModelNetFewShot.__getitem__ (datasets/ModelNetDatasetFewShot.py:59-71: the item and a fresh
+ *   shuffle of its points) and the resample of tools/runner_finetune.py:158-176 (FPS to point_all points, a host draw of
+ *   npoints of them, the gather) in ONE launch from the resident episode to the step's input.
+ * set (s,p,c) f32 with c >= 3: the episode's clouds; item (b) i32: the cloud of each batch row; perm (b,p) i32: a
+ *   permutation of 0..p-1 per row, nullable = the identity; slot (m) i32: the output row of FPS column j or -1,
+ *   nullable = the identity (then npoints must equal m); out (b,npoints,3) f32; idx (b,m) i32, nullable.
+ * With sh[b][k] = set[item[b]][perm[b][k]][0:3] and f = pdae_furthest_point_sampling of sh to m points (first index 0,
+ *   the skipped-point rule, the tie order by the position k in the SHUFFLED cloud):
+ *     idx[b][j] = perm[b][f[b][j]];   out[b][slot[j]] = sh[b][f[b][j]] for every j with 0 <= slot[j] < npoints.
+ *   Coordinates are moved, not computed on: the result equals the existing entry on the materialised shuffle bit for
+ *   bit, signed zeros included.  Rows of out that no slot names are left as they were.
+ * Bad indices fault nothing: a perm entry outside 0..p-1 is not followed -- that position reads as the point (0,0,0),
+ *   which the skipped-point rule never selects (idx still copies the entry); a slot outside 0..npoints-1 writes
+ *   nothing; a row whose item is outside 0..s-1 gets out = NaN and idx = -1.  Two columns with one slot: either.
+ * s, p <= 0, negative b / m / npoints, c < 3, m > p, slot == NULL with npoints != m, a null required pointer:
+ *   PDAE_ERR_BAD_ARG; p > 8192: PDAE_ERR_UNSUPPORTED; b == 0 or m == 0: nothing to do.  All before anything is launched. */
+int pdae_fewshot_batch(int s, int p, int c, int b, int m, int npoints, const float* set, const int32_t* item,
+                       const int32_t* perm /*nullable*/, const int32_t* slot /*nullable*/, float* out,
+                       int32_t* idx /*nullable*/, pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Measurement aids: box calibration for bench.py (csrc/calib.hip). They replace nothing of the reference; the training
  * step never calls them.  MI355X boxes differ by +-4 % on the step and by up to 12 % on matrix loops (the clock a device
  * holds under load), so a bench line carries the rates of two kernels of known work next to its headline.

@@ -22,6 +22,7 @@ python generators are not reproducible across worker counts either.
 Sources: a directory of .npy clouds listed by `<DATA_PATH>/<subset>.txt` (the reference layout), else
 synthetic ShapeNet-shaped clouds (there is no dataset in the image).
 """
+import functools
 import math
 import os
 
@@ -635,3 +636,101 @@ class ModelNet:
         for i in range(0, end, self.bs):
             x = self.x[i:i + self.bs]
             yield 'ModelNet', i, (self.augment(x) if self.aug_type else x, self.y[i:i + self.bs])
+
+
+def pc_normalize(pc):
+    """datasets/ModelNetDatasetFewShot.py:21-26, the reference's numpy expression in the array's own precision."""
+    centroid = np.mean(pc, axis=0)
+    pc = pc - centroid
+    m = np.max(np.sqrt(np.sum(pc ** 2, axis=1)))
+    pc = pc / m
+    return pc
+
+
+@functools.lru_cache(maxsize=2)                 # (the train and the test loader of a run ask for the same episode)
+def synthetic_episode(seed, way, shot, fold, n_points, eval_sample=20):
+    """An episode built the way datasets/generate_few_shot_data.py builds one, from synthetic.labelled_clouds: `way`
+    classes, `shot` training and `eval_sample` test clouds of each, labels 0..way-1, both lists shuffled; a function of
+    (seed, way, shot, fold).  labelled_clouds knows three primitive families: class i is family i % 3, flattened along z
+    by 1 / (1 + i // 3) and normalised again, so that classes of one family still differ.
+    -> {'train': [(points (n_points,3) f32, label, key)], 'test': [...]}, the reference's pickle format."""
+    rng = np.random.default_rng([int(seed), int(way), int(shot), int(fold)])
+    need = shot + eval_sample
+    lists = {'train': [], 'test': []}
+    for i in range(way):
+        got = []
+        while len(got) < need:
+            x, y = labelled_clouds(3 * need, n_points, seed=int(rng.integers(1 << 31)), classes=3)
+            got += list(x[y == i % 3])
+        for n, pts in enumerate(got[:need]):
+            pts = pts * np.array([1.0, 1.0, 1.0 / (1 + i // 3)], np.float32)
+            lists['train' if n < shot else 'test'].append((pc_normalize(pts).astype(np.float32), i, i))
+    return {k: [v[j] for j in rng.permutation(len(v))] for k, v in lists.items()}
+
+
+@DATASETS.register_module()
+class ModelNetFewShot:
+    """One few-shot episode (datasets/ModelNetDatasetFewShot.py of the reference), resident on the device.
+
+    Source: `<DATA_PATH>/<way>way_<shot>shot/<fold>.pkl`, the reference's pickle -- {'train' / 'test': [(points (P, 3 or
+    6), label, key)]} -- when it exists, else synthetic_episode.  pc_normalize runs once per cloud at load, on the host
+    (the reference's workers re-fork from the un-normalised parent every epoch, so once per cloud is what its default
+    run computes); USE_NORMALS false keeps three channels.  way, shot or fold of -1: RuntimeError, as there.  The
+    config's aug_type is accepted and ignored, as in the reference's class.
+
+    `train` yields ('ModelNet', 'sample', (item (bs,) i32, perm (bs, P) i32, labels (bs,) i64)) -- the batch is
+    self.set[item] with row b's points in the order perm[b]; fewshot_ops turns it into the step's input: the items of an
+    epoch are torch.randperm on the seeded device generator, floor(S / bs) full batches, and per batch
+    torch.rand(bs, P).argsort(1) is the point shuffle.  `test` yields ('ModelNet', 'sample', (points (b, P, C), labels
+    (b,))) in list order, the short last batch kept, nothing drawn."""
+
+    fewshot = True
+
+    def __init__(self, config):
+        self.subset = config.get('subset', 'train')
+        self.bs = config.get('bs', 32)
+        self.device = config.get('device', 'cuda')
+        self.seed = int(config.get('seed', 0))
+        self.way, self.shot, self.fold = (int(config.get(k, -1)) for k in ('way', 'shot', 'fold'))
+        if self.way == -1 or self.shot == -1 or self.fold == -1:
+            raise RuntimeError('ModelNetFewShot: --way, --shot and --fold are required')
+        use_normals = config.get('USE_NORMALS', False)
+        use_normals = use_normals.lower() == 'true' if isinstance(use_normals, str) else bool(use_normals)
+        path = os.path.join(str(config.get('DATA_PATH', '')), '%dway_%dshot' % (self.way, self.shot), '%d.pkl' % self.fold)
+        self.listed = os.path.exists(path)
+        if self.listed:
+            import pickle
+            with open(path, 'rb') as f:
+                items = pickle.load(f)[self.subset]
+        else:
+            n_points = int(config.get('N_POINTS', config.get('npoints', 8192)))
+            items = synthetic_episode(self.seed, self.way, self.shot, self.fold, n_points)[self.subset]
+        clouds = []
+        for points, _, _ in items:
+            points = np.array(points)                                   # (a copy: the list keeps the stored cloud)
+            points[:, 0:3] = pc_normalize(points[:, 0:3])
+            clouds.append((points if use_normals else points[:, 0:3]).astype(np.float32))
+        self.set = torch.from_numpy(np.ascontiguousarray(np.stack(clouds, 0))).to(self.device)
+        self.labels = torch.from_numpy(np.array([int(np.asarray(label).reshape(-1)[0]) for _, label, _ in items],
+                                                np.int64)).to(self.device)
+        self.count = self.set.shape[0]
+        self.aug_type = ['norm']              # (runner_finetune.fps_cacheable: the clouds are the same on every pass)
+        self.gen = torch.Generator(device=self.set.device)
+        self.gen.manual_seed(self.seed)
+
+    def __len__(self):
+        if self.subset == 'train':
+            return self.count // self.bs
+        return (self.count + self.bs - 1) // self.bs
+
+    def __iter__(self):
+        dev, P = self.set.device, self.set.shape[1]
+        if self.subset != 'train':
+            for i in range(0, self.count, self.bs):
+                yield 'ModelNet', 'sample', (self.set[i:i + self.bs], self.labels[i:i + self.bs])
+            return
+        order = torch.randperm(self.count, generator=self.gen, device=dev)
+        for i in range(len(self)):
+            item = order[i * self.bs:(i + 1) * self.bs]
+            perm = torch.rand((self.bs, P), generator=self.gen, device=dev).argsort(1).to(torch.int32)
+            yield 'ModelNet', 'sample', (item.to(torch.int32), perm, self.labels.index_select(0, item))

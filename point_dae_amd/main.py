@@ -2,8 +2,8 @@
 (main.py:16-111 of the reference): pretraining, or with --finetune_model / --scratch_model the
 classification fine-tuning runner (--so3_rotation: its rotation-robustness protocol; --svm_classification: the linear-SVM
 evaluation of the frozen encoder; --task_affinity: the linear probe whose test loss ranks corruptions; --vote: a ten-vote
-validation behind a high plain one), or with --test --ckpts the evaluation of a fine-tuned checkpoint: the plain accuracy,
-then --vote_rounds rounds of ten-vote evaluation."""
+validation behind a high plain one; --way/--shot/--fold: one fold of few-shot fine-tuning), or with --test --ckpts the
+evaluation of a fine-tuned checkpoint: the plain accuracy, then --vote_rounds rounds of ten-vote evaluation."""
 import torch
 
 from . import dist_utils, parser
@@ -12,11 +12,33 @@ from .misc import set_random_seed
 from . import runner_finetune, runner_pretrain
 
 
+def apply_fewshot_args(args, config):
+    """main.py:85-91 of the reference: with --shot given, --way / --shot / --fold go into the train and the val dataset
+    node (and into the test node where the config has one: the fine-tuning loop validates on it)."""
+    if args.shot == -1:
+        return config
+    for subset in ('train', 'val', 'test'):
+        node = config.dataset.get(subset)
+        if node is None:
+            continue
+        node.others.shot, node.others.way, node.others.fold = args.shot, args.way, args.fold
+    return config
+
+
 def main(argv=None):
     args = parser.get_args(argv)
+    fewshot = args.shot != -1
+    if fewshot:
+        # (the three lines utils/parse_test_res.py --few-shot reads from a redirected log, next to '[Validation] ... acc = ')
+        print('args.way : %d' % args.way)
+        print('args.shot : %d' % args.shot)
+        print('args.fold : %d' % args.fold)
     args.use_gpu = torch.cuda.is_available()
     if not args.use_gpu:
         raise RuntimeError('point_dae_amd needs an MI355X: there is no CPU path')
+    if fewshot and args.launcher != 'none':
+        # an episode is 50 to 200 clouds: one process, as the other small protocols
+        raise ValueError('few-shot fine-tuning (--way/--shot/--fold) runs in one process: --launcher none')
     if args.svm_classification and args.launcher != 'none':
         # the reference runs this protocol in ONE process under DataParallel (rerun.sh); its distributed branch would fit
         # every rank's SVMs on that rank's shard of the features
@@ -48,6 +70,7 @@ def main(argv=None):
     assert config.total_bs % args.world_size == 0
     config.dataset.train.others.bs = config.total_bs // args.world_size
     set_random_seed(args.seed + args.local_rank, deterministic=args.deterministic)   # main.py:78-81
+    apply_fewshot_args(args, config)                                                 # main.py:85-91
     if args.test:
         runner_finetune.test_net(args, config)                             # main.py:94-95
     elif finetune and args.svm_classification:

@@ -32,6 +32,9 @@ def get_args(argv=None):
                    help='linear-SVM evaluation of the frozen encoder: SVC(kernel=linear) for C = 1e-3 .. 1e2')
     p.add_argument('--task_affinity', action='store_true', default=False,
                    help='evaluate task affinity with pre-trained encoder.')
+    p.add_argument('--way', type=int, default=-1, help='few-shot fine-tuning: classes of the episode (5 or 10)')
+    p.add_argument('--shot', type=int, default=-1, help='few-shot fine-tuning: training clouds per class (10 or 20)')
+    p.add_argument('--fold', type=int, default=-1, help='few-shot fine-tuning: which of the ten episodes (0-9)')
     # synthetic-data controls (no dataset ships with this repo)
     p.add_argument('--max_epoch', type=int, default=-1, help='override config.max_epoch')
     p.add_argument('--steps_per_epoch', type=int, default=None,
@@ -49,6 +52,10 @@ def get_args(argv=None):
         raise ValueError('--vote_rounds must not be negative')
     if args.resume and args.start_ckpts is not None:
         raise ValueError('--resume and --start_ckpts cannot be both activate')
+    given = [name for name in ('way', 'shot', 'fold') if getattr(args, name) != -1]
+    if given and len(given) != 3:
+        raise ValueError('few-shot fine-tuning needs --way, --shot and --fold together (given: %s)'
+                         % ', '.join('--' + name for name in given))
     if args.finetune_model and args.scratch_model:
         raise ValueError('--finetune_model and --scratch_model cannot be both activate')
     if 'LOCAL_RANK' not in os.environ:

@@ -19,6 +19,11 @@ test_net / test_vote / validate_vote (:686-748, :835-899, :568-632; main.py --te
 checkpoint by voting: per test cloud ten subsets of its FPS order, each through test_transforms and the model, the mean of
 the logits.  vote_pass runs one such pass on vote_ops (csrc/vote.hip); FPS is kept per test batch across passes, the hits
 are counted on the device and test_net reads its rounds' counters once.
+
+Few-shot fine-tuning (main.py --way/--shot/--fold, datasets.ModelNetFewShot) is run_net on one resident episode: the
+train loader yields the draws of a batch (items, a fresh point shuffle per row) and fewshot_train_points makes the step's
+input of them -- fewshot_ops (csrc/fewshot.hip): one launch --; the test loader's FPS-to-npoints point sets are taken once
+per fold (fewshot_point_sets) and every later validation runs only the forward.
 """
 import time
 
@@ -75,6 +80,25 @@ def resample(points, npoints, choice=None, point_all=None):
     return gather_operation(xyz.transpose(1, 2).contiguous(), idx).transpose(1, 2).contiguous()
 
 
+def fewshot_train_points(train_loader, data, npoints, out=None):
+    """The training batch of a few-shot episode from the loader's draws data = (item, perm, labels): FPS of every row's
+    shuffled cloud to point_all points and the host draw of npoints of them (runner_finetune.py:158-176).
+    PDAE_FEWSHOT=hip: fewshot_ops.fill_batch, one launch into `out` (a fresh buffer when None) -> out; torch:
+    fewshot_ops.materialise + resample -> a new (B, npoints, 3) tensor.  Both take the same host draw."""
+    from . import fewshot_ops
+    if npoints not in POINT_ALL:
+        raise NotImplementedError('npoints %d' % npoints)
+    item, perm = data[0], data[1]
+    set_ = train_loader.set
+    point_all = min(POINT_ALL[npoints], set_.shape[1])
+    choice = subset_indices(npoints, point_all)
+    if fewshot_ops.backend() == 'torch':
+        return resample(fewshot_ops.materialise(set_, item, perm), npoints, choice=choice)
+    if out is None:
+        out = torch.empty((item.shape[0], npoints, 3), dtype=torch.float32, device=set_.device)
+    return fewshot_ops.fill_batch(set_, item, perm, choice, point_all, out)
+
+
 def train_step(model, optimizer, clip, points, labels):
     """One optimisation step: forward, loss, backward, [gradient all-reduce], clip coefficient, AdamW.
     -> (loss, acc) device scalars."""
@@ -89,13 +113,33 @@ def train_step(model, optimizer, clip, points, labels):
     return loss.detach(), acc.detach()
 
 
-def _predict(base_model, test_loader, config, args=None):
-    """One pass over the test loader: FPS to npoints, eval forward, argmax -> (pred, label) of every test cloud [of every
-    rank]."""
-    preds, labels = [], []
+def fewshot_point_sets(test_loader, npoints):
+    """The FPS-to-npoints point sets of a few-shot test loader, [(points (b, npoints, C), label (b,))] per batch: the test
+    subset is never shuffled, so they are the same on every epoch of a fold and are taken once.  PDAE_FEWSHOT=hip:
+    pdae_fewshot_batch with perm = slot = NULL; torch: misc.fps."""
+    from . import fewshot_ops
+    sets = []
     for _, _, data in test_loader:
         points, label = data[0].cuda(), data[1].cuda()
-        _, points = fps(points, config.npoints)
+        if fewshot_ops.backend() == 'hip' and points.shape[2] == 3:
+            points = fewshot_ops.fps_points(points, npoints)
+        else:
+            _, points = fps(points, npoints)
+        sets.append((points, label))
+    return sets
+
+
+def _predict(base_model, test_loader, config, args=None, point_sets=None):
+    """One pass over the test loader: FPS to npoints, eval forward, argmax -> (pred, label) of every test cloud [of every
+    rank].  point_sets: a list that keeps the FPS-to-npoints point sets of a loader that repeats itself exactly (a
+    few-shot test loader): filled by the first pass (fewshot_point_sets), later passes run only the forward."""
+    preds, labels = [], []
+    if point_sets is not None and not point_sets:
+        point_sets.extend(fewshot_point_sets(test_loader, config.npoints))
+    for _, _, data in (test_loader if point_sets is None else ((None, None, d) for d in point_sets)):
+        points, label = data[0].cuda(), data[1].cuda()
+        if point_sets is None:
+            _, points = fps(points, config.npoints)
         preds.append(base_model(points).argmax(-1).view(-1))
         labels.append(label.view(-1))
     pred, label = torch.cat(preds), torch.cat(labels)
@@ -105,10 +149,11 @@ def _predict(base_model, test_loader, config, args=None):
 
 
 @torch.no_grad()
-def validate(base_model, test_loader, epoch, config, args=None, log=print):
-    """runner_finetune.py:273-318: FPS to npoints, eval forward, argmax accuracy over the whole test set."""
+def validate(base_model, test_loader, epoch, config, args=None, log=print, point_sets=None):
+    """runner_finetune.py:273-318: FPS to npoints, eval forward, argmax accuracy over the whole test set.  point_sets:
+    _predict's list of kept point sets (few-shot: the test loader repeats itself exactly)."""
     base_model.eval()
-    pred, label = _predict(base_model, test_loader, config, args)
+    pred, label = _predict(base_model, test_loader, config, args, point_sets)
     acc = float((pred == label).sum().item()) / float(label.numel()) * 100.
     log('[Validation] EPOCH: %d  acc = %.4f' % (epoch, acc))
     return Acc_Metric(acc)
@@ -310,8 +355,19 @@ def _run(args, config, log, log_every, train_transform=None, validate_fn=validat
     if train_transform is not None:
         from .data_transforms import resample_transformed
     graphed = GraphedClassifierStep(model, optimizer, clip, bs, config.npoints)
+    # few-shot (--way/--shot/--fold): the train loader yields (item, perm, labels) of the resident episode
+    # (fewshot_train_points); the test loader's FPS-to-npoints point sets are taken once per fold
+    fewshot = bool(getattr(train_loader, 'fewshot', False))
+    if fewshot and train_transform is not None:
+        raise NotImplementedError('runner_finetune: few-shot episodes with a train transform (--so3_rotation)')
+    if getattr(test_loader, 'fewshot', False) and validate_fn is validate:
+        import functools
+        validate_fn = functools.partial(validate, point_sets=[])
     if rank == 0:
         log('step: hipGraph replay (GraphedClassifierStep)')
+        if fewshot:
+            from . import fewshot_ops
+            log('Few-shot backend: %s' % fewshot_ops.backend())
         if train_transform is not None:
             log('train transform: %s inside the resample; validation: %s' % (type(train_transform).__name__, validate_fn.__name__))
 
@@ -324,7 +380,13 @@ def _run(args, config, log, log_every, train_transform=None, validate_fn=validat
         acc_sum = torch.zeros(2, device=device)
         t0, n = time.time(), 0
         for idx, (_, _, data) in enumerate(train_loader):
-            if train_transform is None:
+            if fewshot:
+                points = fewshot_train_points(train_loader, data, config.npoints, out=graphed.points)
+                if points is graphed.points:                     # hip: the launch wrote the step's input
+                    loss, acc = graphed.step_filled(data[2])
+                else:                                            # torch: the reference's loop made a tensor of its own
+                    loss, acc = graphed(points, data[2])
+            elif train_transform is None:
                 points = resample(data[0], config.npoints)
                 loss, acc = graphed(points, data[1])             # (the train loader yields only full batches)
             else:
