@@ -1122,6 +1122,25 @@ int pdae_fewshot_batch(int s, int p, int c, int b, int m, int npoints, const flo
                        int32_t* idx /*nullable*/, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The augmented training batch of a resident labelled set (csrc/fewshot.hip; datasets.ModelNet on the reference's
+ * processed ModelNet40 files).
+ * Replaces, per batch row, ModelNet.__getitem__ (datasets/ModelNetDataset.py:127-158: the item, augment_data's per-access
+ *   maps, a fresh shuffle of its points) and the resample of tools/runner_finetune.py:158-176 in ONE launch.
+ * pdae_fewshot_batch with per-row affine maps in front of the FPS: nmaps (b) i32, nullable, and maps (b,3,12) f32 in
+ *   pdae_pipeline_norm_affine's layout (M 3x3 row-major, then t).  With T_b = maps 0 .. nmaps[b]-1 of row b applied in
+ *   order, each as x' = ((x*m00 + y*m10) + z*m20) + t0 (y', z' alike; every operation rounded, no contraction),
+ *     sh[b][k] = T_b(set[item[b]][perm[b][k]][0:3]),
+ *   and FPS, the skipped-point rule, the tie order, idx, slot and out are pdae_fewshot_batch's on sh: out holds the mapped
+ *   coordinates.  nmaps == NULL: pdae_fewshot_batch bit for bit.  With maps: bit for bit the chain item select,
+ *   permutation gather, pdae_pipeline_norm_affine(normalise = 0), pdae_fewshot_batch -- signed zeros included.
+ * Bad indices fault nothing: as pdae_fewshot_batch (the (0,0,0) a bad perm entry reads as is NOT mapped and is never
+ *   selected); a row whose nmaps is outside 0..3 gets out = NaN and idx = -1, like a row whose item is out of range.
+ * Argument errors are pdae_fewshot_batch's; nmaps without maps: PDAE_ERR_BAD_ARG.  All before anything is launched. */
+int pdae_resident_batch(int s, int p, int c, int b, int m, int npoints, const float* set, const int32_t* item,
+                        const int32_t* perm /*nullable*/, const int32_t* nmaps /*nullable*/, const float* maps /*(b,3,12)*/,
+                        const int32_t* slot /*nullable*/, float* out, int32_t* idx /*nullable*/, pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Measurement aids: box calibration for bench.py (csrc/calib.hip). They replace nothing of the reference; the training
  * step never calls them.  MI355X boxes differ by +-4 % on the step and by up to 12 % on matrix loops (the clock a device
  * holds under load), so a bench line carries the rates of two kernels of known work next to its headline.

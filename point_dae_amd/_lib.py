@@ -146,6 +146,7 @@ _SIGNATURES = {
     "pdae_vote_resample": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_vote_reduce": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_fewshot_batch": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_resident_batch": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_calib_mfma_bf16": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_calib_copy": [ctypes.c_longlong, _vp, _vp, _vp],
 }

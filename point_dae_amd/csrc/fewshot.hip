@@ -11,16 +11,26 @@
 // The body is a kernel of its own and not a template parameter of fps_kernel: with the results leaving behind the loop
 // it is no longer the same loop (fps_kernel's thread 0 stores idxs / centres every iteration), and fps_kernel's
 // instantiations -- the pretraining step's FPS -- stay the code they were (few-shot).
+//
+// pdae_resident_batch (the augmented ModelNet40 training batch from the resident set: datasets/ModelNetDataset.py:127-158,
+// augment_data's per-access maps in front of the shuffle) is this kernel with the compile-time flag MAPS; both entries
+// share the argument checks and the ladder (fewshot_dispatch), and pdae_fewshot_batch launches MAPS = false.
 #include <cmath>
+#include <cstdio>
 
 #include "common.h"
 
 namespace pdae {
 
-template <int T, int P>
+// MAPS (pdae_resident_batch): row b's point is sent through its nmaps[b] <= 3 affine maps y = x M + t, one after the other
+// with norm_affine_kernel's arithmetic (pipeline.hip), between the load and everything that looks at the coordinates --
+// the skipped-point rule, the registers, the LDS copy.  The maps are block-uniform values read in the load phase only: the
+// serial loop below is the same code in both instantiations.
+template <int T, int P, bool MAPS>
 __global__ __launch_bounds__(T) void fewshot_batch_kernel(int s, int p, int c, int m, int npoints, int bs_log2, int cols,
                                                           const float* __restrict__ set, const int32_t* __restrict__ item,
-                                                          const int32_t* __restrict__ perm, const int32_t* __restrict__ slot,
+                                                          const int32_t* __restrict__ perm, const int32_t* __restrict__ nmaps,
+                                                          const float* __restrict__ maps, const int32_t* __restrict__ slot,
                                                           float* __restrict__ out, int32_t* __restrict__ idx) {
   constexpr int W = T / kWave;
   extern __shared__ float lds_xyz[];  // p*3 floats, then m picked positions (int)
@@ -32,7 +42,9 @@ __global__ __launch_bounds__(T) void fewshot_batch_kernel(int s, int p, int c, i
   const int it = item[b];
   out += (size_t)b * npoints * 3;
   if (idx) idx += (size_t)b * m;
-  if ((unsigned)it >= (unsigned)s) {  // block-uniform, in front of every barrier: the row is marked, nothing is read
+  const int nm = MAPS ? nmaps[b] : 0;
+  // block-uniform, in front of every barrier: the row is marked, nothing is read
+  if ((unsigned)it >= (unsigned)s || (MAPS && (unsigned)nm > 3u)) {
     const float nan = __builtin_nanf("");
     for (int i = tid; i < npoints * 3; i += T) out[i] = nan;
     if (idx)
@@ -57,6 +69,15 @@ __global__ __launch_bounds__(T) void fewshot_batch_kernel(int s, int p, int c, i
         x = q[0];
         y = q[1];
         z = q[2];
+        if (MAPS) {
+          for (int a = 0; a < nm; ++a) {
+            const float* M = maps + ((size_t)b * 3 + a) * 12;
+            const float x0 = x, y0 = y, z0 = z;
+            x = ((x0 * M[0] + y0 * M[3]) + z0 * M[6]) + M[9];  // row vector times matrix, then t: norm_affine_kernel's order
+            y = ((x0 * M[1] + y0 * M[4]) + z0 * M[7]) + M[10];
+            z = ((x0 * M[2] + y0 * M[5]) + z0 * M[8]) + M[11];
+          }
+        }
         const float mag = (x * x) + (y * y) + (z * z);
         valid = !((double)mag <= 1e-3);
       }
@@ -128,33 +149,40 @@ static int fewshot_ref_block_size(int work_size) {
 
 template <int T, int P>
 static void launch_fewshot(int s, int p, int c, int b, int m, int npoints, int bs_log2, int cols, const float* set,
-                           const int32_t* item, const int32_t* perm, const int32_t* slot, float* out, int32_t* idx,
-                           hipStream_t st) {
+                           const int32_t* item, const int32_t* perm, const int32_t* nmaps, const float* maps,
+                           const int32_t* slot, float* out, int32_t* idx, hipStream_t st) {
   const size_t lds_bytes = (size_t)p * 3 * sizeof(float) + (size_t)m * sizeof(int);
-  hipLaunchKernelGGL((fewshot_batch_kernel<T, P>), dim3(b), dim3(T), lds_bytes, st, s, p, c, m, npoints, bs_log2, cols, set,
-                     item, perm, slot, out, idx);
+  if (nmaps)
+    hipLaunchKernelGGL((fewshot_batch_kernel<T, P, true>), dim3(b), dim3(T), lds_bytes, st, s, p, c, m, npoints, bs_log2,
+                       cols, set, item, perm, nmaps, maps, slot, out, idx);
+  else
+    hipLaunchKernelGGL((fewshot_batch_kernel<T, P, false>), dim3(b), dim3(T), lds_bytes, st, s, p, c, m, npoints, bs_log2,
+                       cols, set, item, perm, nmaps, maps, slot, out, idx);
 }
 
-}  // namespace pdae
-
-extern "C" int pdae_fewshot_batch(int s, int p, int c, int b, int m, int npoints, const float* set, const int32_t* item,
-                                  const int32_t* perm, const int32_t* slot, float* out, int32_t* idx,
-                                  pdae_stream_t stream) {
-  using namespace pdae;
-  if (s <= 0 || p <= 0 || b < 0 || m < 0 || npoints < 0) return bad_arg("fewshot_batch: s>0, p>0, b>=0, m>=0, npoints>=0 required");
-  if (c < 3) return bad_arg("fewshot_batch: c >= 3 (the first three channels are the coordinates)");
-  if (m > p) return bad_arg("fewshot_batch: m > p");
-  if (!slot && npoints != m) return bad_arg("fewshot_batch: without slot, npoints must equal m");
+// the argument checks and the T/P ladder both entries share; `what` prefixes the messages.  nmaps == NULL: no maps.
+static int fewshot_dispatch(const char* what, int s, int p, int c, int b, int m, int npoints, const float* set,
+                            const int32_t* item, const int32_t* perm, const int32_t* nmaps, const float* maps,
+                            const int32_t* slot, float* out, int32_t* idx, pdae_stream_t stream) {
+  char msg[160];
+#define PDAE_FEWSHOT_FAIL(fn, text) return (snprintf(msg, sizeof msg, "%s: %s", what, text), fn(msg))
+  if (s <= 0 || p <= 0 || b < 0 || m < 0 || npoints < 0) PDAE_FEWSHOT_FAIL(bad_arg, "s>0, p>0, b>=0, m>=0, npoints>=0 required");
+  if (c < 3) PDAE_FEWSHOT_FAIL(bad_arg, "c >= 3 (the first three channels are the coordinates)");
+  if (m > p) PDAE_FEWSHOT_FAIL(bad_arg, "m > p");
+  if (!slot && npoints != m) PDAE_FEWSHOT_FAIL(bad_arg, "without slot, npoints must equal m");
+  if (nmaps && !maps) PDAE_FEWSHOT_FAIL(bad_arg, "nmaps without maps");
   if (b == 0 || m == 0) return PDAE_OK;
-  if (!set || !item || !out) return bad_arg("fewshot_batch: null pointer");
-  if (p > 8192) return unsupported("fewshot_batch: p > 8192 not implemented (the episodes' clouds have 8192 points)");
+  if (!set || !item || !out) PDAE_FEWSHOT_FAIL(bad_arg, "null pointer");
+  if (p > 8192) PDAE_FEWSHOT_FAIL(unsupported, "p > 8192 not implemented (the clouds have 8192 points)");
+#undef PDAE_FEWSHOT_FAIL
   const int bs = fewshot_ref_block_size(p);
   int bs_log2 = 0;
   while ((1 << bs_log2) < bs) ++bs_log2;
   const int cols = (p + bs - 1) / bs;
   hipStream_t st = as_stream(stream);
   // the T/P ladder of pdae_furthest_point_sampling
-#define PDAE_FEWSHOT_LAUNCH(T, P) launch_fewshot<T, P>(s, p, c, b, m, npoints, bs_log2, cols, set, item, perm, slot, out, idx, st)
+#define PDAE_FEWSHOT_LAUNCH(T, P) \
+  launch_fewshot<T, P>(s, p, c, b, m, npoints, bs_log2, cols, set, item, perm, nmaps, maps, slot, out, idx, st)
   if (p <= 64) PDAE_FEWSHOT_LAUNCH(64, 1);
   else if (p <= 128) PDAE_FEWSHOT_LAUNCH(64, 2);
   else if (p <= 256) PDAE_FEWSHOT_LAUNCH(128, 2);
@@ -164,5 +192,23 @@ extern "C" int pdae_fewshot_batch(int s, int p, int c, int b, int m, int npoints
   else if (p <= 4096) PDAE_FEWSHOT_LAUNCH(1024, 4);
   else PDAE_FEWSHOT_LAUNCH(1024, 8);
 #undef PDAE_FEWSHOT_LAUNCH
-  return check_launch("fewshot_batch");
+  return check_launch(what);
+}
+
+}  // namespace pdae
+
+extern "C" int pdae_fewshot_batch(int s, int p, int c, int b, int m, int npoints, const float* set, const int32_t* item,
+                                  const int32_t* perm, const int32_t* slot, float* out, int32_t* idx,
+                                  pdae_stream_t stream) {
+  return pdae::fewshot_dispatch("fewshot_batch", s, p, c, b, m, npoints, set, item, perm, nullptr, nullptr, slot, out, idx,
+                                stream);
+}
+
+// The augmented training batch of a resident set (datasets.ModelNet on the reference's files): pdae_fewshot_batch with the
+// per-row maps of augment_data in front of the FPS.
+extern "C" int pdae_resident_batch(int s, int p, int c, int b, int m, int npoints, const float* set, const int32_t* item,
+                                   const int32_t* perm, const int32_t* nmaps, const float* maps, const int32_t* slot,
+                                   float* out, int32_t* idx, pdae_stream_t stream) {
+  return pdae::fewshot_dispatch("resident_batch", s, p, c, b, m, npoints, set, item, perm, nmaps, maps, slot, out, idx,
+                                stream);
 }

@@ -214,13 +214,19 @@ def _dev(a, device, dtype=None):
 def pipeline_norm_affine(x, normalise=False, maps=None, sigma=None, noise=None, stride=None):
     """x (B,P,3) -> y (B,stride,3) with rows [0,P) = jitter(affine maps(norm(x))) (csrc/pipeline.hip norm_affine).
     maps: list per cloud of up to three (M (3,3), t (3,)) pairs applied in order, y = x M + t; sigma (B,) and
-    noise (B,P,3) on the device: y += sigma * noise."""
+    noise (B,P,3) on the device: y += sigma * noise.  maps may also be the packed pair (nmaps (B,) int32,
+    maps (B,3,12) float32: M row-major, then t) already on the device."""
     B, P, _ = x.shape
     stride = P if stride is None else stride
     dev = x.device
     y = torch.empty((B, stride, 3), device=dev)
     nm = mp = None
-    if maps is not None:
+    if isinstance(maps, tuple):
+        nm, mp = maps
+        if tuple(nm.shape) != (B,) or nm.dtype != torch.int32 or tuple(mp.shape) != (B, 3, 12) or mp.dtype != torch.float32:
+            raise ValueError('pipeline_norm_affine: packed maps are nmaps (B,) int32 and maps (B,3,12) float32')
+        nm, mp = nm.contiguous(), mp.contiguous()
+    elif maps is not None:
         packed = np.zeros((B, 3, 12), np.float32)
         packed[:, :, 0] = packed[:, :, 4] = packed[:, :, 8] = 1.0
         counts = np.zeros(B, np.int32)
@@ -575,17 +581,45 @@ class ShapeNetClass(ShapeNet):
 
 @DATASETS.register_module()
 class ModelNet:
-    """Labelled clouds for the SVM probe (datasets/ModelNetDataset.py of the reference yields
-    (taxonomy, model_id, (points, label))).  No ModelNet40 files ship with the image: labelled synthetic
-    clouds stand in (synthetic.labelled_clouds); `count` clouds, batches of `bs`, resident on the device.  The `train`
-    subset drops a short last batch, as the reference's train loader does (tools/builder.py: drop_last)."""
+    """Labelled clouds for the classification protocols (datasets/ModelNetDataset.py of the reference yields
+    (taxonomy, model_id, (points, label))), resident on the device, batches of `bs`.  The `train` subset drops a short
+    last batch, as the reference's train loader does (tools/builder.py: drop_last).
+
+    Source: the reference's processed file `<DATA_PATH>/modelnet<NUM_CATEGORY>_<subset>_<N_POINTS>pts_fps.dat`
+    (ModelNetDataset.py:93) -- a pickle of [list_of_points, list_of_labels], every cloud (N_POINTS, 6) float32, every
+    label an int32 array of one element -- when it exists (`listed`); else labelled synthetic clouds
+    (synthetic.labelled_clouds, `count` of them), exactly as before the file was ever looked for.  The first-run
+    .txt -> .dat conversion and ModelNet_Official (HDF5) are not read.
+
+    A listed set: `count` keeps the file's first clouds; USE_NORMALS false keeps columns 0..2; a leading 'norm' of
+    aug_type is applied once per cloud at load with pc_normalize (a pure function of the stored cloud: what the
+    reference's default run computes on every access), the remaining items are per-access maps.  set (S,P,C) f32 and
+    labels (S,) i64 live on the device, on every rank.  Its `train` subset does on every access what the reference's
+    loader does (ModelNetDataset.py:127-158, tools/builder.py:17-31): the items are shuffled once per epoch
+    (epoch_items), every cloud gets fresh maps and a fresh shuffle of its points.  Two ways to iterate it, which consume
+    the generators identically:
+        iter_draws()  ('ModelNet', 'sample', (item (bs,) i32, perm (bs,P) i32, nmaps (bs,) i32, maps (bs,3,12) f32, labels))
+                      -- resident_ops turns the draws into the step's input in one launch; offered when `resident`
+        __iter__      ('ModelNet', i, (points (bs,P,C), labels)): the same draws as framework ops -- item select, the
+                      maps through pipeline_norm_affine, the permutation gather
+    More than three per-access maps, or a 'norm' that is not first, go through `augment` inside __iter__; `resident` is
+    then False.  The other subsets yield every cloud in file order, the short last batch kept."""
 
     def __init__(self, config):
         self.npoints = config.get('npoints', 1024)
         self.bs = config.get('bs', 32)
-        self.count = config.get('count', 256)
         self.subset = config.get('subset', 'test')
         self.device = config.get('device', 'cuda')
+        self.listed, self.resident = False, False
+        path = None
+        if config.get('DATA_PATH'):
+            path = os.path.join(str(config.get('DATA_PATH')), 'modelnet%d_%s_%dpts_fps.dat' % (
+                int(config.get('NUM_CATEGORY', 40)), self.subset, int(config.get('N_POINTS', self.npoints))))
+        if path is not None and os.path.exists(path):
+            self._init_listed(config, path)
+            return
+        self.source = 'synthetic stand-in (no %s)' % (path if path is not None else 'DATA_PATH')
+        self.count = config.get('count', 256)
         seed = config.get('seed', 0) + (1000 if self.subset == 'train' else 2000)
         # `classes`: how many of the NUM_CATEGORY labels the synthetic clouds use (default 3)
         classes = int(config.get('classes', min(3, config.get('NUM_CATEGORY', 3))))
@@ -603,11 +637,104 @@ class ModelNet:
             if item not in _AUGS:
                 raise NotImplementedError('augmentation %r (implemented: %s)' % (item, ', '.join(_AUGS)))
         self.rng = np.random.default_rng(seed + 17) if self.aug_type else None
+        self.access = self.aug_type
+
+    def _init_listed(self, config, path):
+        """The reference's processed file: the set and its labels on the device, a leading 'norm' applied at load."""
+        import pickle
+        with open(path, 'rb') as f:
+            points, labels = pickle.load(f)
+        count = config.get('count', None)
+        if count is not None:
+            points, labels = points[:int(count)], labels[:int(count)]
+        use_normals = config.get('USE_NORMALS', False)
+        use_normals = use_normals.lower() == 'true' if isinstance(use_normals, str) else bool(use_normals)
+        self.aug_type = [a for a in config.get('aug_type', ['clean']) if a != 'clean']
+        for item in self.aug_type:
+            if item not in _AUGS:
+                raise NotImplementedError('augmentation %r (implemented: %s)' % (item, ', '.join(_AUGS)))
+        # per-access items: what is left behind a leading 'norm'.  Up to three maps and no further 'norm' is what one launch
+        # of norm_affine / pdae_resident_batch takes; anything else keeps the whole list for `augment`
+        rest = self.aug_type[1:] if self.aug_type[:1] == ['norm'] else self.aug_type
+        fused = len(rest) <= 3 and 'norm' not in rest
+        self.access = rest if fused else self.aug_type
+        norm_at_load = fused and self.aug_type[:1] == ['norm']
+        clouds = []
+        for pts in points:
+            pts = np.array(pts, np.float32)                              # (a copy: the pickle's list keeps the stored cloud)
+            if norm_at_load:
+                pts[:, 0:3] = pc_normalize(pts[:, 0:3])
+            clouds.append(pts if use_normals else pts[:, 0:3])
+        x = np.ascontiguousarray(np.stack(clouds, 0))
+        y = np.array([int(np.asarray(label).reshape(-1)[0]) for label in labels], np.int64)
+        self.seed = int(config.get('seed', 0))
+        self.rank, self.world = int(config.get('rank', 0)), max(int(config.get('world', 1)), 1)
+        if self.subset != 'train' and self.world > 1:   # DistributedSampler(shuffle=False), as for the synthetic clouds
+            sel = np.resize(np.arange(len(x)), -(-len(x) // self.world) * self.world)[self.rank::self.world]
+            x, y = x[sel], y[sel]
+        self.count = len(x)
+        self.set = self.x = torch.from_numpy(x).to(self.device)
+        self.labels = self.y = torch.from_numpy(y).to(self.device)
+        self.listed = True
+        self.resident = self.subset == 'train' and fused
+        self.source = '%s (%d clouds of %d points, %d channels)' % (path, self.count, x.shape[1], x.shape[2])
+        self.rng = np.random.default_rng(self.seed + (1000 if self.subset == 'train' else 2000) + 17)
+        self.gen = torch.Generator(device=self.set.device)
+        self.gen.manual_seed(self.seed)
+        self._epoch, self._epoch_set = -1, False
 
     def __len__(self):
+        if self.listed and self.subset == 'train':       # DistributedSampler pads to ceil(S / world); drop_last
+            return -(-self.count // self.world) // self.bs
         if self.subset == 'train':                       # the reference's train loader: drop_last (tools/builder.py)
             return self.count // self.bs
         return (self.count + self.bs - 1) // self.bs
+
+    def set_epoch(self, epoch):
+        """DistributedSampler.set_epoch: the next iteration of a listed train subset draws epoch `epoch`'s permutation;
+        without it the epochs count from 0."""
+        self._epoch, self._epoch_set = int(epoch), True
+
+    def draw_maps(self, B):
+        """The per-access maps of B clouds, draw_affine_map(rng, 'aug_' + item) cloud by cloud, in pdae_pipeline_norm_affine's
+        layout -> (nmaps (B,) int32, maps (B,3,12) float32: M 3x3 row-major then t; unused entries the identity), host."""
+        packed = np.zeros((B, 3, 12), np.float32)
+        packed[:, :, 0] = packed[:, :, 4] = packed[:, :, 8] = 1.0
+        for b in range(B):
+            for q, item in enumerate(self.access):
+                M, t = draw_affine_map(self.rng, 'aug_' + item)
+                packed[b, q, :9], packed[b, q, 9:] = M.reshape(-1), t
+        return np.full(B, len(self.access), np.int32), packed
+
+    def iter_draws(self):
+        """One epoch of a listed train subset as draws: ('ModelNet', 'sample', (item, perm, nmaps, maps, labels)), all on
+        the device.  The batch is T_b(set[item[b]][perm[b]]) with T_b row b's nmaps[b] maps in order."""
+        if not self.resident:
+            raise RuntimeError('ModelNet.iter_draws: a listed train subset whose per-access augmentation is at most three '
+                               'maps (resident) is required')
+        return self._draws()
+
+    def _draws(self):
+        dev, P = self.set.device, self.set.shape[1]
+        if not self._epoch_set:
+            self._epoch += 1
+        self._epoch_set = False
+        items = epoch_items(self.count, self.seed - self.rank, self._epoch, self.rank, self.world, self.bs)
+        for row in items:
+            item = _dev(row.astype(np.int32), dev)
+            perm = torch.rand((self.bs, P), generator=self.gen, device=dev).argsort(1).to(torch.int32)
+            if self.resident:
+                nmaps, maps = self.draw_maps(self.bs)
+                nmaps, maps = _dev(nmaps, dev), _dev(maps, dev)
+            else:
+                nmaps = maps = None
+            yield 'ModelNet', 'sample', (item, perm, nmaps, maps, self.labels.index_select(0, item.long()))
+
+    def _mapped(self, x, fn):
+        """fn on the coordinates of x (B,P,C), the other channels untouched."""
+        if x.shape[2] == 3:
+            return fn(x.contiguous())
+        return torch.cat([fn(x[:, :, :3].contiguous()), x[:, :, 3:]], 2)
 
     def augment(self, x):
         """augment_data of one batch on csrc/pipeline.hip: a 'norm' normalises everything drawn before it first (the kernel
@@ -620,7 +747,7 @@ class ModelNet:
                 x = pipeline_norm_affine(x, norm_pending, [m[:3] for m in maps] if any(maps) else None)
                 maps, norm_pending = [m[3:] for m in maps], False
             return x
-        for item in self.aug_type:
+        for item in self.access:
             if item == 'norm':
                 x = flush(x, norm_pending, maps)
                 maps, norm_pending = [[] for _ in range(B)], True
@@ -630,12 +757,38 @@ class ModelNet:
         return flush(x, norm_pending, maps)
 
     def __iter__(self):
+        if self.listed and self.subset == 'train':
+            # the draws of iter_draws as framework ops: item select, the maps, the permutation gather
+            C = self.set.shape[2]
+            for i, (_, _, (item, perm, nmaps, maps, labels)) in enumerate(self._draws()):
+                x = self.set.index_select(0, item.long())
+                if self.resident:
+                    x = self._mapped(x, lambda xyz: pipeline_norm_affine(xyz, False, (nmaps, maps)))
+                elif self.access:
+                    x = self._mapped(x, self.augment)
+                x = torch.gather(x, 1, perm.long().unsqueeze(-1).expand(-1, -1, C)).contiguous()
+                yield 'ModelNet', i * self.bs, (x, labels)
+            return
         # a train subset yields only full batches, as the reference's DataLoader(drop_last=True) does; every other
         # subset yields every cloud, its last batch short
         end = len(self) * self.bs if self.subset == 'train' else self.count
         for i in range(0, end, self.bs):
             x = self.x[i:i + self.bs]
-            yield 'ModelNet', i, (self.augment(x) if self.aug_type else x, self.y[i:i + self.bs])
+            if self.access:
+                x = self._mapped(x, self.augment) if self.listed else self.augment(x)
+            yield 'ModelNet', i, (x, self.y[i:i + self.bs])
+
+
+def epoch_items(count, seed, epoch, rank, world, bs):
+    """The items of one epoch of a listed train loader on one rank, as DistributedSampler(shuffle=True) + DataLoader(
+    drop_last=True) arrange them (tools/builder.py:17-31): ONE permutation of 0..count-1 from a generator seeded with
+    (seed, epoch) -- `seed` is the one all ranks share --, wrap-padded to a multiple of world, rank r takes [r::world],
+    floor(n / bs) full batches.  -> (batches, bs) int64."""
+    shared = np.random.default_rng([int(seed), int(epoch)]).permutation(int(count))
+    world = max(int(world), 1)
+    mine = np.resize(shared, -(-int(count) // world) * world)[int(rank)::world]
+    full = len(mine) // int(bs)
+    return mine[:full * bs].reshape(full, bs).astype(np.int64)
 
 
 def pc_normalize(pc):

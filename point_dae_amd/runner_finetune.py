@@ -24,6 +24,11 @@ Few-shot fine-tuning (main.py --way/--shot/--fold, datasets.ModelNetFewShot) is 
 train loader yields the draws of a batch (items, a fresh point shuffle per row) and fewshot_train_points makes the step's
 input of them -- fewshot_ops (csrc/fewshot.hip): one launch --; the test loader's FPS-to-npoints point sets are taken once
 per fold (fewshot_point_sets) and every later validation runs only the forward.
+
+A ModelNet loader on the reference's processed files (datasets.ModelNet, `listed`) shuffles its items per epoch and redraws
+every cloud's maps and point shuffle per access; under PDAE_MODELNET=hip its draws go through resident_train_points --
+resident_ops (csrc/fewshot.hip, pdae_resident_batch): one launch into the step's input --, and a test loader that repeats
+itself exactly keeps its point sets the way the few-shot one does.
 """
 import time
 
@@ -99,6 +104,20 @@ def fewshot_train_points(train_loader, data, npoints, out=None):
     return fewshot_ops.fill_batch(set_, item, perm, choice, point_all, out)
 
 
+def resident_train_points(train_loader, data, npoints, out):
+    """The training batch of a resident ModelNet loader from its draws data = (item, perm, nmaps, maps, labels)
+    (datasets.ModelNet.iter_draws): the maps, the shuffle, FPS to point_all points and the host draw of npoints of them,
+    by one launch into `out` (resident_ops.fill_batch, csrc/fewshot.hip) -> out."""
+    from . import resident_ops
+    if npoints not in POINT_ALL:
+        raise NotImplementedError('npoints %d' % npoints)
+    item, perm, nmaps, maps = data[:4]
+    set_ = train_loader.set
+    point_all = min(POINT_ALL[npoints], set_.shape[1])
+    choice = subset_indices(npoints, point_all)
+    return resident_ops.fill_batch(set_, item, perm, nmaps, maps, choice, point_all, out)
+
+
 def train_step(model, optimizer, clip, points, labels):
     """One optimisation step: forward, loss, backward, [gradient all-reduce], clip coefficient, AdamW.
     -> (loss, acc) device scalars."""
@@ -116,13 +135,16 @@ def train_step(model, optimizer, clip, points, labels):
 def fewshot_point_sets(test_loader, npoints):
     """The FPS-to-npoints point sets of a few-shot test loader, [(points (b, npoints, C), label (b,))] per batch: the test
     subset is never shuffled, so they are the same on every epoch of a fold and are taken once.  PDAE_FEWSHOT=hip:
-    pdae_fewshot_batch with perm = slot = NULL; torch: misc.fps."""
-    from . import fewshot_ops
+    pdae_fewshot_batch with perm = slot = NULL; torch: misc.fps.  A listed ModelNet test loader without per-access
+    augmentation (fps_cacheable) is kept the same way, under PDAE_MODELNET."""
+    from . import fewshot_ops, resident_ops
+    # (a listed ModelNet test loader keeps its point sets the same way, under PDAE_MODELNET)
+    ops = fewshot_ops if getattr(test_loader, 'fewshot', False) else resident_ops
     sets = []
     for _, _, data in test_loader:
         points, label = data[0].cuda(), data[1].cuda()
-        if fewshot_ops.backend() == 'hip' and points.shape[2] == 3:
-            points = fewshot_ops.fps_points(points, npoints)
+        if ops.backend() == 'hip' and points.shape[2] == 3:
+            points = ops.fps_points(points, npoints)
         else:
             _, points = fps(points, npoints)
         sets.append((points, label))
@@ -256,6 +278,7 @@ def test_net(args, config, log=print):
     device = torch.device('cuda', torch.cuda.current_device())
     log('Tester start ... ')
     test_loader = _loader(config.dataset.test, device, args.seed, 0, 1, config.total_bs)
+    _log_sources(log, None, test_loader)
     base_model = builder.model_builder(config.model)
     builder.load_model(base_model, args.ckpts)
     base_model = base_model.to(device).eval()
@@ -296,6 +319,13 @@ def _loader(node, device, seed, rank, world, bs, steps_per_epoch=None):
         c.update(count=steps_per_epoch * bs)
     c.setdefault('bs', bs)
     return DATASETS.build(c)
+
+
+def _log_sources(log, train_loader, test_loader):
+    """One line per ModelNet loader saying where its clouds come from: the reference's processed file or the stand-in."""
+    for name, loader in (('train', train_loader), ('test', test_loader)):
+        if getattr(loader, 'source', None) is not None:
+            log('ModelNet %s source: %s' % (name, loader.source))
 
 
 def run_net(args, config, log=print, log_every=20):
@@ -360,11 +390,20 @@ def _run(args, config, log, log_every, train_transform=None, validate_fn=validat
     fewshot = bool(getattr(train_loader, 'fewshot', False))
     if fewshot and train_transform is not None:
         raise NotImplementedError('runner_finetune: few-shot episodes with a train transform (--so3_rotation)')
-    if getattr(test_loader, 'fewshot', False) and validate_fn is validate:
+    # a ModelNet loader on the reference's files (datasets.ModelNet, `listed`): the train loader's draws go through
+    # resident_train_points under PDAE_MODELNET=hip; a test loader that repeats itself exactly keeps its point sets
+    from . import resident_ops
+    offered = bool(getattr(train_loader, 'resident', False)) and not fewshot and train_transform is None
+    resident = offered and resident_ops.backend() == 'hip'
+    keep_sets = getattr(test_loader, 'fewshot', False) or (getattr(test_loader, 'listed', False) and fps_cacheable(test_loader))
+    if keep_sets and validate_fn is validate:
         import functools
         validate_fn = functools.partial(validate, point_sets=[])
     if rank == 0:
         log('step: hipGraph replay (GraphedClassifierStep)')
+        _log_sources(log, train_loader, test_loader)
+        if offered:
+            log('ModelNet backend: %s' % resident_ops.backend())
         if fewshot:
             from . import fewshot_ops
             log('Few-shot backend: %s' % fewshot_ops.backend())
@@ -379,8 +418,11 @@ def _run(args, config, log, log_every, train_transform=None, validate_fn=validat
             train_loader.set_epoch(epoch)
         acc_sum = torch.zeros(2, device=device)
         t0, n = time.time(), 0
-        for idx, (_, _, data) in enumerate(train_loader):
-            if fewshot:
+        for idx, (_, _, data) in enumerate(train_loader.iter_draws() if resident else train_loader):
+            if resident:
+                resident_train_points(train_loader, data, config.npoints, out=graphed.points)
+                loss, acc = graphed.step_filled(data[4])
+            elif fewshot:
                 points = fewshot_train_points(train_loader, data, config.npoints, out=graphed.points)
                 if points is graphed.points:                     # hip: the launch wrote the step's input
                     loss, acc = graphed.step_filled(data[2])
@@ -446,6 +488,7 @@ def _frozen_features(args, config, log):
     train_loader = _loader(config.dataset.train, device, args.seed + rank, rank, world, bs,
                            getattr(args, 'steps_per_epoch', None))
     test_loader = _loader(config.dataset.val, device, args.seed, rank, world, bs)
+    _log_sources(log, train_loader, test_loader)
     base_model = builder.model_builder(config.model)
     if getattr(args, 'resume', False):
         builder.resume_model(base_model, args)
