@@ -475,6 +475,13 @@ int pdae_group_sum_listed(int n_listed, int C, const float* X, const int32_t* gr
 int pdae_group_gemm_scatter(int M, int N, int K, const float* X, const int32_t* a_groups, const float* W,
                             const float* gbias, float* Y, int ldy, const int32_t* c_groups,
                             pdae_stream_t stream);
+/*   group_gemm_scatter_add: group_gemm_scatter, and the gradient of the max over a group's 32 points (:47 torch.max)
+ *       lands where the rows are stored: Y[g*32 + sarg[g][n]][n] receives + sgrad[g][n] for every destination group
+ *       g = c_groups[m/32] (sgrad, sarg: [groups of Y][N]; both NULL: group_gemm_scatter).  Bit for bit the rows that
+ *       group_gemm_scatter followed by group_scatter_add leaves. */
+int pdae_group_gemm_scatter_add(int M, int N, int K, const float* X, const int32_t* a_groups, const float* W,
+                                const float* gbias, float* Y, int ldy, const int32_t* c_groups, const float* sgrad,
+                                const unsigned char* sarg, pdae_stream_t stream);
 
 /* Set-abstraction levels of the PointNet++ encoder (Point_CAE_PointNetv2;
  * extensions/pointnet2/pointnet2_modules.py PointnetSAModule: SharedMLP of
@@ -638,8 +645,15 @@ int pdae_embed_bnrelu_conv_store_groupmax(int M, int N, int K, const float* X,
                                           float* Y, float* gmax,
                                           unsigned char* garg,
                                           pdae_stream_t stream);
+/*   embed_bnrelu_conv_store_groupmax_sum  (first_conv[1..3] + the max of :47, for a step whose backward takes the
+ *       masked-groups algebra above) the same Y, gmax, garg, and gsum[M/32,N] = the sum over each group's 32 rows of
+ *       Y out of the same epilogue, the rows added in row order: bit for bit group_sum_listed's sums, the fsum of
+ *       that algebra without a sweep over Y. */
+int pdae_embed_bnrelu_conv_store_groupmax_sum(int M, int N, int K, const float* X, const float* scale, const float* shift,
+                                              const float* W, const float* bias, float* Y, float* gmax,
+                                              unsigned char* garg, float* gsum, pdae_stream_t stream);
 
-/*   embed_conv1_stats   first_conv[0] (:24, Conv1d(3, C, 1)) on rows (R,3):
+/*   embed_conv1_stats  first_conv[0] (:24, Conv1d(3, C, 1)) on rows (R,3):
  *       y[R,C] = x.W^T + bias, evaluated as ((x0*w0 + x1*w1) + x2*w2) + b, and
  *       stats[0][c] += sum y, stats[1][c] += sum y*y in fp64 (caller zeroes
  *       stats before the first call; C/4 must divide 256).
@@ -659,6 +673,14 @@ int pdae_embed_conv1_stats(int R, int C, const float* x, const float* W,
 int pdae_embed_conv1_backward_weight_parts(int R);
 int pdae_embed_conv1_backward_weight(int R, int C, const float* d, const float* x, float* part,
                                      pdae_stream_t stream);
+/* embed_bnrelu_backward_conv1_weight: bnrelu_backward_apply on first_conv[1..2] (:25-26 BatchNorm1d + ReLU; R = 32 G rows,
+ * sums S given) and embed_conv1_backward_weight on first_conv[0] (:24) in one pass: d (R, C) is READ ONLY, the gradient of
+ * the conv output is formed per element by bnrelu_backward_apply's expression and consumed by embed_conv1_backward_weight's
+ * row walk without being stored (the K = 3 conv has no data gradient).  part is bit for bit what the two entries leave. */
+int pdae_embed_bnrelu_backward_conv1_weight(int R, int C, const float* d, const float* y1, const float* scale,
+                                            const float* shift, const float* mean, const float* invstd,
+                                            const float* gamma, const float* S, const float* x, float* part,
+                                            pdae_stream_t stream);
 int pdae_bn_finalize(int C, long long rows, const double* stats64 /*nullable*/,
                      const float* partials /*nullable*/, int P,
                      const float* gamma, const float* beta, float eps,
@@ -860,6 +882,11 @@ int pdae_embed_split_conv3_weight(int N, int K2, const float* w, float* wg, floa
                                   pdae_stream_t stream);
 int pdae_embed_masked_prep(int Gm, int C3, int C2, const float* uv, const float* gb, const int32_t* masked, const float* wl,
                            float* xe, float* wv, pdae_stream_t stream);
+/*   embed_masked_prep_fsum   embed_masked_prep (point_dae_amd/patch_embed.py _masked_by_algebra; Encoder,
+ *                     models/PointCAE_transformer.py:37-51) whose launch also gathers fsum_m (Gm, C2) = gsum[masked] from
+ *                     embed_bnrelu_conv_store_groupmax_sum's group sums gsum (BG, C2). */
+int pdae_embed_masked_prep_fsum(int Gm, int C3, int C2, const float* uv, const float* gb, const int32_t* masked, const float* wl,
+                                float* xe, float* wv, const float* gsum, float* fsum_m, pdae_stream_t stream);
 int pdae_embed_dw3_assemble(int C3, int C2, const float* dwg, const float* dwl, const float* v /*nullable*/,
                             const float* wgram /*nullable*/, const float* xterm /*nullable*/, float* dw3, pdae_stream_t stream);
 /*   scale_colsum        Y = keep[row/T] * X and out[c] (nullable) = column sums

@@ -52,6 +52,7 @@ _SIGNATURES = {
     "pdae_embed_conv_groupbias_stats": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_bnrelu_conv_groupmax": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_bnrelu_conv_store_groupmax": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_embed_bnrelu_conv_store_groupmax_sum": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_group_max_scatter": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_group_scatter_add": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_bnrelu_backward": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
@@ -75,11 +76,13 @@ _SIGNATURES = {
     "pdae_scale_colsum": [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
     "pdae_embed_conv1_stats": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_conv1_backward_weight": [_i, _i, _vp, _vp, _vp, _vp],
+    "pdae_embed_bnrelu_backward_conv1_weight": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_bn_finalize": [_i, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_adamw_step": [ctypes.c_longlong, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp],
     "pdae_masked_group_sums": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_group_sum_listed": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_group_gemm_scatter": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
+    "pdae_group_gemm_scatter_add": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "pdae_conv_stats": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_bnrelu_group_max": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_group_max_scatter_n": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp],
@@ -120,6 +123,7 @@ _SIGNATURES = {
     "pdae_assemble_tokens_grad": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "pdae_embed_split_conv3_weight": [_i, _i, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_masked_prep": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_embed_masked_prep_fsum": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_embed_dw3_assemble": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_adamw_step_gscale": [ctypes.c_longlong, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp, _vp],
     "pdae_prepend_token": [_i, _i, _i, _vp, _vp, _vp, _vp],

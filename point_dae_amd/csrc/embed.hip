@@ -10,6 +10,8 @@
 //   bnrelu_backward_apply  dX = gamma*invstd * (t - S1/R - xhat*S2/R), in place
 //                          over dA, plus the per-group row sums of dX (needed by
 //                          the global half of the split concat GEMM)
+//   bnrelu_backward_conv1_weight  BatchNorm-1's apply formed inside the first conv's weight
+//                          gradient: the (R, C) gradient of the conv output is never stored
 // All are float4-wide, one pass over each operand.
 #include "common.h"
 
@@ -47,6 +49,19 @@ __global__ __launch_bounds__(256) void group_scatter_add_kernel(int G, int C,
   if (i >= (long long)G * C) return;
   const int g = (int)(i / C), c = (int)(i - (long long)g * C);
   dst[((size_t)g * 32 + arg[i]) * C + c] += grad[i];
+}
+
+// the same for the groups groups[0 .. n_listed) of a dst with row stride ld
+__global__ __launch_bounds__(256) void group_scatter_add_listed_kernel(int n_listed, int C, int ld,
+                                                                       const float* __restrict__ grad,
+                                                                       const unsigned char* __restrict__ arg,
+                                                                       const int* __restrict__ groups,
+                                                                       float* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)n_listed * C) return;
+  const int cg = (int)(i / C), c = (int)(i - (long long)cg * C);
+  const size_t o = (size_t)groups[cg] * C + c;
+  dst[((size_t)groups[cg] * 32 + arg[o]) * ld + c] += grad[o];
 }
 
 // column sums over a slab of rows; thread owns 4 columns, 8 row lanes per block
@@ -239,7 +254,7 @@ __global__ __launch_bounds__(256) void group_sum_listed_kernel(int n_listed, int
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long long)n_listed * C4) return;
   const int cg = (int)(i / C4), q = (int)(i - (long long)cg * C4);
-  const float4* row = X + (size_t)groups[cg] * 32 * C4 + q;
+  const float4* row = X + (size_t)(groups ? groups[cg] : cg) * 32 * C4 + q;     // (no list: every group)
   float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 8
   for (int r = 0; r < 32; ++r) {
@@ -361,6 +376,24 @@ extern "C" int pdae_group_scatter_add(int G, int C, const float* grad, const uns
 }
 
 namespace pdae {
+// (gemm.hip: the sweeps behind embed_bnrelu_conv_store_groupmax_sum / group_gemm_scatter_add where the epilogue form does not run)
+int group_sum_all(hipStream_t s, int G, int C, const float* X, float* out) {
+  const long long n = (long long)G * (C / 4);
+  if (n == 0) return PDAE_OK;
+  hipLaunchKernelGGL(group_sum_listed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, G, C / 4,
+                     reinterpret_cast<const float4*>(X), static_cast<const int*>(nullptr), reinterpret_cast<float4*>(out));
+  return check_launch("group_sum_all");
+}
+
+int group_scatter_add_listed(hipStream_t s, int n_listed, int C, int ld, const float* grad, const unsigned char* arg,
+                             const int* groups, float* dst) {
+  const long long n = (long long)n_listed * C;
+  if (n == 0) return PDAE_OK;
+  hipLaunchKernelGGL(group_scatter_add_listed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_listed, C, ld,
+                     grad, arg, groups, dst);
+  return check_launch("group_scatter_add_listed");
+}
+
 int bnrelu_backward_sums(hipStream_t s, int Rsum, int C, const float* dA, const float* X, const float* scale, const float* shift,
                          const float* mean, const float* invstd, float* S, const int* groups) {
   (void)hipMemsetAsync(S, 0, sizeof(float) * 2 * (size_t)C, s);
@@ -564,4 +597,107 @@ extern "C" int pdae_embed_conv1_backward_weight(int R, int C, const float* d, co
                      sizeof(float4) * 3 * 256, as_stream(stream), R, C / 4, reinterpret_cast<const float4*>(d), x,
                      reinterpret_cast<float4*>(part));
   return check_launch("embed_conv1_backward_weight");
+}
+
+// BatchNorm-1 + ReLU backward and the first conv's weight gradient in ONE pass: the gradient of the conv output,
+// bnrelu_backward_apply_kernel's expression element for element, goes straight into conv1_backward_weight_kernel's
+// row walk (the same blocks, row phases, per-thread order of adds and LDS meeting order) and is never stored -- the
+// K = 3 conv has no data gradient, so the weight gradient was its only reader.  part equals what the two launches leave.
+namespace pdae {
+__global__ __launch_bounds__(256) void bnrelu_backward_conv1_weight_kernel(
+    int R, int C4, const float4* __restrict__ d, const float4* __restrict__ y1, const float4* __restrict__ scale,
+    const float4* __restrict__ shift, const float4* __restrict__ mean, const float4* __restrict__ invstd,
+    const float4* __restrict__ gamma, const float4* __restrict__ S, float inv_rows, const float* __restrict__ x,
+    float4* __restrict__ part) {
+  extern __shared__ float4 c1b_red[];             // [phases][3][C4]
+  const int PH = 256 / C4;
+  const int q = threadIdx.x % C4, ph = threadIdx.x / C4;
+  const float4 sc = scale[q], sh = shift[q], mu = mean[q], is = invstd[q], ga = gamma[q], s1 = S[q], s2 = S[C4 + q];
+  const float kx = ga.x * is.x, ky = ga.y * is.y, kz = ga.z * is.z, kw = ga.w * is.w;
+  const float m1x = s1.x * inv_rows, m1y = s1.y * inv_rows, m1z = s1.z * inv_rows, m1w = s1.w * inv_rows;
+  const float m2x = s2.x * inv_rows, m2y = s2.y * inv_rows, m2z = s2.z * inv_rows, m2w = s2.w * inv_rows;
+  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0;
+  const int r0 = blockIdx.x * C1B_ROWS, r1 = min(R, r0 + C1B_ROWS);
+  auto acc = [&](const float4& t, const float4& v, float x0, float x1, float x2) __attribute__((always_inline)) {
+    float4 g;
+    g.x = kx * (((v.x * sc.x + sh.x > 0.f) ? t.x : 0.f) - m1x - ((v.x - mu.x) * is.x) * m2x);
+    g.y = ky * (((v.y * sc.y + sh.y > 0.f) ? t.y : 0.f) - m1y - ((v.y - mu.y) * is.y) * m2y);
+    g.z = kz * (((v.z * sc.z + sh.z > 0.f) ? t.z : 0.f) - m1z - ((v.z - mu.z) * is.z) * m2z);
+    g.w = kw * (((v.w * sc.w + sh.w > 0.f) ? t.w : 0.f) - m1w - ((v.w - mu.w) * is.w) * m2w);
+    a0.x += g.x * x0, a0.y += g.y * x0, a0.z += g.z * x0, a0.w += g.w * x0;
+    a1.x += g.x * x1, a1.y += g.y * x1, a1.z += g.z * x1, a1.w += g.w * x1;
+    a2.x += g.x * x2, a2.y += g.y * x2, a2.z += g.z * x2, a2.w += g.w * x2;
+  };
+  // The walk has one block of four waves per 1024 rows (the partials' layout), so a CU's bytes in flight are what a thread
+  // requests ahead: batches of U rows of both operands, the next batch requested before the current one is added (a plain
+  // loop unrolled four times moved 2.7 TB/s).  The adds keep the rows' order.
+  constexpr int U = 8;
+  float4 ta[U], va[U], tb[U], vb[U];
+  float xa[U][3], xb[U][3];
+  auto fetch = [&](int rr, float4 (&t)[U], float4 (&v)[U], float (&xx)[U][3]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t row = (size_t)(rr + u * PH);
+      t[u] = d[row * C4 + q];
+      v[u] = y1[row * C4 + q];
+      xx[u][0] = x[row * 3], xx[u][1] = x[row * 3 + 1], xx[u][2] = x[row * 3 + 2];
+    }
+  };
+  auto add = [&](const float4 (&t)[U], const float4 (&v)[U], const float (&xx)[U][3]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc(t[u], v[u], xx[u][0], xx[u][1], xx[u][2]);
+  };
+  int r = r0 + ph;
+  const int step = U * PH, last = (U - 1) * PH;          // a batch at r is whole when r + last < r1
+  if (r + last < r1) {
+    fetch(r, ta, va, xa);
+    for (;;) {
+      const bool more_b = r + step + last < r1;
+      if (more_b) fetch(r + step, tb, vb, xb);
+      add(ta, va, xa);
+      r += step;
+      if (!more_b) break;
+      const bool more_a = r + step + last < r1;
+      if (more_a) fetch(r + step, ta, va, xa);
+      add(tb, vb, xb);
+      r += step;
+      if (!more_a) break;
+    }
+  }
+  for (; r < r1; r += PH)
+    acc(d[(size_t)r * C4 + q], y1[(size_t)r * C4 + q], x[(size_t)r * 3], x[(size_t)r * 3 + 1], x[(size_t)r * 3 + 2]);
+  c1b_red[(ph * 3 + 0) * C4 + q] = a0;
+  c1b_red[(ph * 3 + 1) * C4 + q] = a1;
+  c1b_red[(ph * 3 + 2) * C4 + q] = a2;
+  __syncthreads();
+  if (ph == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      float4 t = c1b_red[k * C4 + q];
+      for (int p = 1; p < PH; ++p) {
+        const float4 u = c1b_red[(p * 3 + k) * C4 + q];
+        t.x += u.x, t.y += u.y, t.z += u.z, t.w += u.w;
+      }
+      part[((size_t)blockIdx.x * 3 + k) * C4 + q] = t;
+    }
+  }
+}
+}  // namespace pdae
+
+extern "C" int pdae_embed_bnrelu_backward_conv1_weight(int R, int C, const float* d, const float* y1, const float* scale,
+                                                       const float* shift, const float* mean, const float* invstd,
+                                                       const float* gamma, const float* S, const float* x, float* part,
+                                                       pdae_stream_t stream) {
+  if (R < 0 || C <= 0 || C % 4 != 0 || C > 1024 || 256 % (C / 4) != 0)
+    return bad_arg("embed_bnrelu_backward_conv1_weight: C/4 must divide 256");
+  if (R == 0) return PDAE_OK;
+  if (!d || !y1 || !scale || !shift || !mean || !invstd || !gamma || !S || !x || !part)
+    return bad_arg("embed_bnrelu_backward_conv1_weight: null pointer");
+  hipLaunchKernelGGL(bnrelu_backward_conv1_weight_kernel, dim3((R + C1B_ROWS - 1) / C1B_ROWS), dim3(256),
+                     sizeof(float4) * 3 * 256, as_stream(stream), R, C / 4, reinterpret_cast<const float4*>(d),
+                     reinterpret_cast<const float4*>(y1), reinterpret_cast<const float4*>(scale),
+                     reinterpret_cast<const float4*>(shift), reinterpret_cast<const float4*>(mean),
+                     reinterpret_cast<const float4*>(invstd), reinterpret_cast<const float4*>(gamma),
+                     reinterpret_cast<const float4*>(S), 1.0f / (float)R, x, reinterpret_cast<float4*>(part));
+  return check_launch("embed_bnrelu_backward_conv1_weight");
 }

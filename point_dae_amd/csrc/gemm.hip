@@ -58,6 +58,10 @@ namespace rows3 {
 bool conv3_takes(const NtArgs& a, int pro, int epi);    // rows3_gemm.hip: the same contracts on exact-split bf16
 void launch_conv3(NtArgs& a, int pro, int epi, hipStream_t s);
 }  // namespace rows3
+// embed.hip: the stand-alone sweeps the folded epilogues replace, for the products conv3_kernel does not take
+int group_sum_all(hipStream_t s, int G, int C, const float* X, float* out);
+int group_scatter_add_listed(hipStream_t s, int n_listed, int C, int ld, const float* grad, const unsigned char* arg,
+                             const int* groups, float* dst);
 }  // namespace pdae
 
 namespace pdae {
@@ -576,4 +580,49 @@ extern "C" int pdae_embed_bnrelu_conv_store_groupmax(int M, int N, int K, const 
   a.M = M, a.N = N, a.K = K, a.A = X, a.lda = K, a.B = W, a.ldb = K, a.C = Y, a.ldc = N, a.bias = bias;
   a.pro_scale = scale, a.pro_shift = shift, a.gmax = gmax, a.garg = garg;
   return launch_nt<PRO_BNRELU, EPI_STORE_GROUPMAX>(a, as_stream(stream));
+}
+
+// embed_bnrelu_conv_store_groupmax with the groups' row sums of Y out of the same epilogue (gsum[M/32,N]); Y, gmax and garg
+// are the plain entry's.  A product conv3_kernel does not take (the fp32-input arithmetic, K % 32 != 0) runs the plain entry
+// and the group-sum sweep.
+extern "C" int pdae_embed_bnrelu_conv_store_groupmax_sum(int M, int N, int K, const float* X, const float* scale,
+                                                         const float* shift, const float* W, const float* bias, float* Y,
+                                                         float* gmax, unsigned char* garg, float* gsum,
+                                                         pdae_stream_t stream) {
+  int rc = check_nt("embed_bnrelu_conv_store_groupmax_sum: bad size", M, N, K);
+  if (rc) return rc;
+  if (M % 32 != 0) return bad_arg("embed_bnrelu_conv_store_groupmax_sum: M must be a multiple of 32");
+  if (M == 0) return PDAE_OK;
+  if (!X || !scale || !shift || !W || !Y || !gmax || !garg || !gsum)
+    return bad_arg("embed_bnrelu_conv_store_groupmax_sum: null pointer");
+  NtArgs a = {};
+  a.M = M, a.N = N, a.K = K, a.A = X, a.lda = K, a.B = W, a.ldb = K, a.C = Y, a.ldc = N, a.bias = bias;
+  a.pro_scale = scale, a.pro_shift = shift, a.gmax = gmax, a.garg = garg, a.gsum = gsum;
+  if (launch_conv3_if<PRO_BNRELU, EPI_STORE_GROUPMAX_SUM>(a, as_stream(stream)))
+    return check_launch("embed_bnrelu_conv_store_groupmax_sum");
+  if (N % 4 != 0) return unsupported("embed_bnrelu_conv_store_groupmax_sum: N must be a multiple of 4 on this arithmetic");
+  rc = launch_nt<PRO_BNRELU, EPI_STORE_GROUPMAX>(a, as_stream(stream));
+  if (rc) return rc;
+  return group_sum_all(as_stream(stream), M / 32, N, Y, gsum);
+}
+
+// group_gemm_scatter with the max-pool gradient added where the rows are stored: row sarg[g][n] of destination group
+// g = c_groups[m/32] receives + sgrad[g][n] (sgrad, sarg: [groups of Y][N], both or neither) -- what group_scatter_add over
+// the listed groups would leave in Y (ldy == N with sgrad).  A product conv3_kernel does not take runs the two launches.
+extern "C" int pdae_group_gemm_scatter_add(int M, int N, int K, const float* X, const int32_t* a_groups, const float* W,
+                                           const float* gbias, float* Y, int ldy, const int32_t* c_groups,
+                                           const float* sgrad, const unsigned char* sarg, pdae_stream_t stream) {
+  int rc = check_nt("group_gemm_scatter_add: bad size", M, N, K);
+  if (rc) return rc;
+  if (M % 32 != 0) return bad_arg("group_gemm_scatter_add: M must be a multiple of 32 (whole groups)");
+  if ((sgrad == nullptr) != (sarg == nullptr)) return bad_arg("group_gemm_scatter_add: sgrad and sarg go together");
+  if (M == 0) return PDAE_OK;
+  if (!X || !W || !Y || !c_groups || ldy < N) return bad_arg("group_gemm_scatter_add: null pointer / bad ldy");
+  NtArgs a = {};
+  a.M = M, a.N = N, a.K = K, a.A = X, a.lda = K, a.B = W, a.ldb = K, a.C = Y, a.ldc = ldy;
+  a.gbias = gbias, a.a_groups = a_groups, a.c_groups = c_groups, a.sgrad = sgrad, a.sarg = sarg;
+  if (launch_conv3_if<PRO_NONE, EPI_GROUP_SCATTER_ADD>(a, as_stream(stream))) return check_launch("group_gemm_scatter_add");
+  rc = pdae_group_gemm_scatter(M, N, K, X, a_groups, W, gbias, Y, ldy, c_groups, stream);
+  if (rc || !sgrad) return rc;
+  return group_scatter_add_listed(as_stream(stream), M / 32, N, ldy, sgrad, sarg, c_groups, Y);
 }

@@ -116,9 +116,11 @@ __global__ __launch_bounds__(256) void split_conv3_weight_kernel(int N, int K2, 
 
 // the element-wise operands of the masked-groups algebra (patch_embed.py _masked_by_algebra):
 //   xe[g][c] = u[c] + gb[masked[g]][c] * v[c]   (Gm, C3)        wv[c][k] = wl[c][k] * v[c]   (C3, C2)
+//   fsum_m[g] = gsum[masked[g]]   (Gm, C2; gsum nullable: the conv2 forward's group sums, gathered by the same launch)
 __global__ __launch_bounds__(256) void masked_prep_kernel(int Gm, int C3, int C2, const float* __restrict__ uv, const float* __restrict__ gb,
                                                           const int* __restrict__ masked, const float* __restrict__ wl,
-                                                          float4* __restrict__ xe, float4* __restrict__ wv) {
+                                                          float4* __restrict__ xe, float4* __restrict__ wv,
+                                                          const float4* __restrict__ gsum, float4* __restrict__ fsum_m) {
   const int q3 = C3 / 4, q2 = C2 / 4;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < Gm * q3) {
@@ -131,6 +133,9 @@ __global__ __launch_bounds__(256) void masked_prep_kernel(int Gm, int C3, int C2
     const float4 w = reinterpret_cast<const float4*>(wl)[j];
     const float v = uv[C3 + c];
     wv[j] = make_float4(w.x * v, w.y * v, w.z * v, w.w * v);
+  } else if (gsum && i < Gm * q3 + C3 * q2 + Gm * q2) {
+    const int j = i - Gm * q3 - C3 * q2, g = j / q2;
+    fsum_m[j] = gsum[(size_t)masked[g] * q2 + (j - g * q2)];
   }
 }
 
@@ -335,8 +340,22 @@ extern "C" int pdae_embed_masked_prep(int Gm, int C3, int C2, const float* uv, c
   if (!uv || !wl || !wv || (Gm > 0 && (!gb || !masked || !xe))) return bad_arg("embed_masked_prep: null pointer");
   const int n = Gm * (C3 / 4) + C3 * (C2 / 4);
   hipLaunchKernelGGL(masked_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), Gm, C3, C2, uv, gb, masked, wl,
-                     reinterpret_cast<float4*>(xe), reinterpret_cast<float4*>(wv));
+                     reinterpret_cast<float4*>(xe), reinterpret_cast<float4*>(wv), static_cast<const float4*>(nullptr),
+                     static_cast<float4*>(nullptr));
   return check_launch("embed_masked_prep");
+}
+
+extern "C" int pdae_embed_masked_prep_fsum(int Gm, int C3, int C2, const float* uv, const float* gb, const int* masked,
+                                           const float* wl, float* xe, float* wv, const float* gsum, float* fsum_m,
+                                           pdae_stream_t stream) {
+  if (Gm < 0 || C3 <= 0 || C2 <= 0 || C3 % 4 != 0 || C2 % 4 != 0) return bad_arg("embed_masked_prep_fsum: widths must be multiples of 4");
+  if ((long long)Gm * C3 + (long long)C3 * C2 + (long long)Gm * C2 >= (1LL << 31)) return bad_arg("embed_masked_prep_fsum: too large");
+  if (!uv || !wl || !wv || (Gm > 0 && (!gb || !masked || !xe || !gsum || !fsum_m))) return bad_arg("embed_masked_prep_fsum: null pointer");
+  const int n = Gm * (C3 / 4) + C3 * (C2 / 4) + Gm * (C2 / 4);
+  hipLaunchKernelGGL(masked_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), Gm, C3, C2, uv, gb, masked, wl,
+                     reinterpret_cast<float4*>(xe), reinterpret_cast<float4*>(wv),
+                     Gm > 0 ? reinterpret_cast<const float4*>(gsum) : nullptr, reinterpret_cast<float4*>(fsum_m));
+  return check_launch("embed_masked_prep_fsum");
 }
 
 extern "C" int pdae_embed_dw3_assemble(int C3, int C2, const float* dwg, const float* dwl, const float* v, const float* wgram,

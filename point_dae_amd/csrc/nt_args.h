@@ -11,8 +11,11 @@ enum {
   EPI_GROUPMAX = 4,
   EPI_STORE_GROUPMAX = 5,
   EPI_STATS = 6,           // C = acc (+ bias); per-column sum / sum of squares like EPI_GROUPBIAS_STATS
-  EPI_GROUP_SCATTER = 7    // C[c_groups[m/32]*32 + m%32] = acc + gbias[m/32] (gbias nullable): whole 32-row groups
+  EPI_GROUP_SCATTER = 7,   // C[c_groups[m/32]*32 + m%32] = acc + gbias[m/32] (gbias nullable): whole 32-row groups
                            // of a compact product land at listed groups of a larger matrix
+  EPI_STORE_GROUPMAX_SUM = 8,  // EPI_STORE_GROUPMAX and gsum[m/32] = the sum over the group's 32 rows of what C receives
+  EPI_GROUP_SCATTER_ADD = 9    // EPI_GROUP_SCATTER with + sgrad[dst group] on the row sarg[dst group] of every column
+                               // (the max-pool gradient added where the rows are stored), dst group = c_groups[m/32]
 };
 
 struct NtArgs {
@@ -33,6 +36,9 @@ struct NtArgs {
   unsigned char* garg;     // [M/32][N]
   const int* a_groups;     // nullable: row m of A is source row a_groups[m/32]*32 + m%32
   const int* c_groups;     // EPI_GROUP_SCATTER: destination group of tile-row group m/32
+  float* gsum;             // [M/32][N]  EPI_STORE_GROUPMAX_SUM
+  const float* sgrad;      // [groups of C][N]  EPI_GROUP_SCATTER_ADD (nullable, with sarg: nothing added)
+  const unsigned char* sarg;  // [groups of C][N]  row in the group that receives sgrad
   int tiles_n, tiles, tile_rows;
 };
 

@@ -25,8 +25,10 @@ static void conv3_launch(NtArgs& a, hipStream_t s) {
 
 // the (producer, epilogue) pairs gemm.hip asks for: the only instantiations of conv3_kernel
 static bool conv3_pair(int pro, int epi) {
-  if (pro == PRO_NONE) return epi == EPI_GROUPBIAS_STATS || epi == EPI_STATS || epi == EPI_GROUP_SCATTER;
-  return pro == PRO_BNRELU && (epi == EPI_STATS || epi == EPI_GROUPMAX || epi == EPI_STORE_GROUPMAX);
+  if (pro == PRO_NONE)
+    return epi == EPI_GROUPBIAS_STATS || epi == EPI_STATS || epi == EPI_GROUP_SCATTER || epi == EPI_GROUP_SCATTER_ADD;
+  return pro == PRO_BNRELU &&
+         (epi == EPI_STATS || epi == EPI_GROUPMAX || epi == EPI_STORE_GROUPMAX || epi == EPI_STORE_GROUPMAX_SUM);
 }
 
 bool conv3_takes(const NtArgs& a, int pro, int epi) {
@@ -42,12 +44,14 @@ void launch_conv3(NtArgs& a, int pro, int epi, hipStream_t s) {
       case EPI_GROUPBIAS_STATS: conv3_launch<PRO_NONE, EPI_GROUPBIAS_STATS>(a, s); break;
       case EPI_STATS: conv3_launch<PRO_NONE, EPI_STATS>(a, s); break;
       case EPI_GROUP_SCATTER: conv3_launch<PRO_NONE, EPI_GROUP_SCATTER>(a, s); break;
+      case EPI_GROUP_SCATTER_ADD: conv3_launch<PRO_NONE, EPI_GROUP_SCATTER_ADD>(a, s); break;
     }
   } else {
     switch (epi) {
       case EPI_STATS: conv3_launch<PRO_BNRELU, EPI_STATS>(a, s); break;
       case EPI_GROUPMAX: conv3_launch<PRO_BNRELU, EPI_GROUPMAX>(a, s); break;
       case EPI_STORE_GROUPMAX: conv3_launch<PRO_BNRELU, EPI_STORE_GROUPMAX>(a, s); break;
+      case EPI_STORE_GROUPMAX_SUM: conv3_launch<PRO_BNRELU, EPI_STORE_GROUPMAX_SUM>(a, s); break;
     }
   }
 }

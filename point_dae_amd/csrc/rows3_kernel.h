@@ -1047,12 +1047,17 @@ __global__ __launch_bounds__(512) void wgrad3t_kernel(const rows::WgradArgs g) {
 //   EPI_STORE_GROUPMAX    C = acc + bias stored; gmax / garg = max over each group's rows and the first row attaining it
 //   EPI_GROUPMAX          the same without the store
 //   EPI_GROUP_SCATTER     C[c_groups[m / 32] * 32 + m % 32] = acc + gbias[m / 32] (gbias nullable)
+//   EPI_STORE_GROUPMAX_SUM  EPI_STORE_GROUPMAX and gsum = the group's sum of the stored values, rows added in row order
+//   EPI_GROUP_SCATTER_ADD   EPI_GROUP_SCATTER, and the row sarg[dst group][col] of every column receives + sgrad[dst group][col]
+//                         after the sum above: the value a scatter-add sweep over the stored rows would leave
 template <int PRO, int EPI>
 __global__ __launch_bounds__(512) void conv3_kernel(const NtArgs p) {
   constexpr int TI = 1, TJ = 2, WM = 4, WN = 2, BM = 128, BN = 128, ROWB = 80, BKT = 32;
   constexpr int PLANE = (BM + BN) * ROWB, BUF = 3 * PLANE;
   constexpr int G = TI * TJ;
   constexpr bool DUAL = true;
+  constexpr bool SCATTER = EPI == EPI_GROUP_SCATTER || EPI == EPI_GROUP_SCATTER_ADD;
+  constexpr bool STOREMAX = EPI == EPI_STORE_GROUPMAX || EPI == EPI_STORE_GROUPMAX_SUM;
   extern __shared__ __attribute__((aligned(16))) char lds3[];   // [2][BUF] tile buffers, then [WM][2][BN] floats of statistics
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -1191,10 +1196,30 @@ __global__ __launch_bounds__(512) void conv3_kernel(const NtArgs p) {
 
   for (;;) {
     const int m0 = (tile / p.tiles_n) * BM, n0 = (tile % p.tiles_n) * BN;
+    // EPI_GROUP_SCATTER_ADD: the row of each of this lane's columns that receives sgrad (none: -1), requested HERE so that the
+    // chain c_groups -> sarg / sgrad travels behind the k-loop (in the epilogue it cost two exposed latencies per tile: 277 ->
+    // 397 us on the step's two launches); the destination group is wave-uniform: read through the scalar cache
+    float sg[TJ];
+    int sa[TJ], dstg = 0;
+    if constexpr (EPI == EPI_GROUP_SCATTER_ADD) {
+      const int grp = __builtin_amdgcn_readfirstlane((m0 + wm * 32) >> 5);
+      if (grp * 32 < M) dstg = p.c_groups[grp];
+    }
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) {
+      sg[j] = 0.f, sa[j] = -1;
+      if constexpr (EPI == EPI_GROUP_SCATTER_ADD) {
+        const int gr = m0 + wm * 32, gc = n0 + (wn * TJ + j) * 32 + r;
+        if (gr < M && gc < N && p.sgrad) {
+          const size_t o = (size_t)dstg * N + gc;
+          sa[j] = p.sarg[o], sg[j] = p.sgrad[o];
+        }
+      }
+    }
 #pragma unroll
     for (int j = 0; j < TJ; ++j) {
       float init = 0.f;
-      if (EPI == EPI_GROUPBIAS_STATS || EPI == EPI_GROUP_SCATTER) {
+      if (EPI == EPI_GROUPBIAS_STATS || SCATTER) {
         const int gr = m0 + wm * 32, gc = n0 + (wn * TJ + j) * 32 + r;
         if (gr < M && gc < N && (EPI == EPI_GROUPBIAS_STATS || p.gbias)) init = p.gbias[(size_t)(gr >> 5) * N + gc];
       }
@@ -1217,30 +1242,31 @@ __global__ __launch_bounds__(512) void conv3_kernel(const NtArgs p) {
       const int col = n0 + (wn * TJ + j) * 32 + r;
       const bool colok = col < N;
       const float bv = (p.bias && colok) ? p.bias[col] : 0.f;
-      const float add = (EPI == EPI_GROUPBIAS_STATS || EPI == EPI_GROUP_SCATTER) ? 0.f : bv;
+      const float add = (EPI == EPI_GROUPBIAS_STATS || SCATTER) ? 0.f : bv;
       float vmax = -__builtin_huge_valf();
       int amax = 0;
       float* cbase = nullptr;
       if (EPI != EPI_GROUPMAX) {
         int crow = rbase;
-        if (EPI == EPI_GROUP_SCATTER && rows_in) crow = p.c_groups[rbase >> 5] * 32;
+        if (SCATTER && rows_in) crow = (EPI == EPI_GROUP_SCATTER_ADD ? dstg : p.c_groups[rbase >> 5]) * 32;
         cbase = p.C + (size_t)(crow + 4 * h) * ldc + col;
       }
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int lr = (e & 3) + 8 * (e >> 2) + 4 * h;
         const bool in = colok && rbase + lr < M;
-        const float v = (hi[0][j][e] + lo[0][j][e]) + add;
+        float v = (hi[0][j][e] + lo[0][j][e]) + add;
+        if (EPI == EPI_GROUP_SCATTER_ADD && lr == sa[j]) v += sg[j];
         if ((EPI == EPI_GROUPBIAS_STATS || EPI == EPI_STATS) && rbase + lr < M) {
           csum[j] += v;
           csq[j] += v * v;
         }
-        if (EPI == EPI_GROUPMAX || EPI == EPI_STORE_GROUPMAX) {
+        if (EPI == EPI_GROUPMAX || STOREMAX) {
           if (v > vmax) vmax = v, amax = lr;            // e ascending => lr ascending within this half
         }
         if (EPI != EPI_GROUPMAX && in) R3_STORE(&cbase[(unsigned)((e & 3) + 8 * (e >> 2)) * ldc], v);
       }
-      if (EPI == EPI_GROUPMAX || EPI == EPI_STORE_GROUPMAX) {
+      if (EPI == EPI_GROUPMAX || STOREMAX) {
         const float ov = __shfl_xor(vmax, 32, kWave);
         const int oa = __shfl_xor(amax, 32, kWave);
         if ((ov > vmax) || (ov == vmax && oa < amax)) vmax = ov, amax = oa;
@@ -1248,6 +1274,36 @@ __global__ __launch_bounds__(512) void conv3_kernel(const NtArgs p) {
           p.gmax[(size_t)(rbase >> 5) * N + col] = vmax;
           p.garg[(size_t)(rbase >> 5) * N + col] = (unsigned char)amax;
         }
+      }
+    }
+    if constexpr (EPI == EPI_STORE_GROUPMAX_SUM) {
+      // the groups' sums of the stored values in the ROW order of group_sum_listed_kernel (0 + row 0 + row 1 + ... + row 31: the
+      // same bits, so a step computes what it computed with that sweep): registers 4k .. 4k + 3 are rows 8k + 4h .. + 3, so
+      // the running sum goes back and forth between a lane (h = 0) and its partner, four rows at a time; both columns' chains
+      // run side by side.  Only what reaches lane h = 0 at the end is a sum: the other halves carry don't-care values.
+      float s[TJ], bj[TJ];
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const int col = n0 + (wn * TJ + j) * 32 + r;
+        s[j] = 0.f, bj[j] = (p.bias && col < N) ? p.bias[col] : 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+#pragma unroll
+          for (int j = 0; j < TJ; ++j) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s[j] += (hi[0][j][4 * k + i] + lo[0][j][4 * k + i]) + bj[j];
+          }
+#pragma unroll
+          for (int j = 0; j < TJ; ++j) s[j] = __shfl_xor(s[j], 32, kWave);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const int col = n0 + (wn * TJ + j) * 32 + r;
+        if (h == 0 && col < N && rows_in) p.gsum[(size_t)(rbase >> 5) * N + col] = s[j];
       }
     }
     if (EPI == EPI_GROUPBIAS_STATS || EPI == EPI_STATS) {

@@ -17,8 +17,9 @@ cuDNN convs and separate BatchNorm / ReLU / max / concat / add passes:
                    bias; the epilogue accumulates BatchNorm's batch statistics;
             conv4: BN2+ReLU applied while A is staged, epilogue keeps only the
                    group max / argmax: the (R, C) product is never written.
-  backward  max-pool / ReLU / BatchNorm backward are three fused sweeps
-            (group_max_scatter, bnrelu_backward, group_scatter_add); weight
+  backward  max-pool / ReLU / BatchNorm backward are fused sweeps
+            (group_max_scatter, bnrelu_backward, group_scatter_add), the last two
+            folded into neighbouring kernels on the masked step (FOLD); weight
             gradients recompute the BN+ReLU activations in the GEMM producer;
             data-gradient GEMMs read the (out, in) weights as [K][N] operands on the row
             GEMM family (csrc/rows_gemm.hip): no transposed copies, no BLAS library.
@@ -38,6 +39,12 @@ from .rows import bn_eval_affine, bn_finalize, colsum, empty, gemm_bnstats, line
 
 # (A/B: 0 = the small element-wise steps of the embedder as framework launches: 2 + 4 + 3 + 2 of them instead of 1 + 1 + 1 + 1)
 GLUE = os.environ.get('PDAE_EMBED_GLUE', os.environ.get('PDAE_GLUE', '1')) != '0'
+
+# (A/B: 0 = the embedder backward's three stand-alone sweeps as their own launches: BatchNorm-1's apply before the first conv's
+#  weight gradient (a), group_sum_listed (b), group_scatter_add (c); 1 = folded into the neighbouring kernels; letters = those alone)
+_fold = os.environ.get('PDAE_EMBED_FOLD', '1').lower()
+FOLD = _fold != '0'
+FOLD_PARTS = ''.join(c for c in 'abc' if c in _fold) or 'abc'
 
 
 DEBUG_KEEP = None       # (lab) a dict: the backward keeps clones of its intermediates in it (tools/lab/model_nondet.py)
@@ -78,9 +85,17 @@ class PatchEmbedFunction(torch.autograd.Function):
         f = empty((R, c2), x)
         g = empty((BG, c2), x)
         arg2 = empty((BG, c2), x, torch.uint8)
-        probed_family('embed_gemm', 2.0 * R * c2 * c1, lambda: _lib.call(
-            'pdae_embed_bnrelu_conv_store_groupmax', x, R, c2, c1, _lib.ptr(y1), _lib.ptr(sc1),
-            _lib.ptr(sh1), _lib.ptr(w2m), _lib.ptr(b2), _lib.ptr(f), _lib.ptr(g), _lib.ptr(arg2)))
+        # (the backward's masked-groups algebra wants the groups' row sums of f: the same epilogue leaves them)
+        algebra = groups is not None and masked is not None and masked.numel() > 0 and training
+        gsum = empty((BG, c2), x) if algebra and FOLD and 'b' in FOLD_PARTS and c2 % 4 == 0 else None
+        if gsum is not None:
+            probed_family('embed_gemm', 2.0 * R * c2 * c1, lambda: _lib.call(
+                'pdae_embed_bnrelu_conv_store_groupmax_sum', x, R, c2, c1, _lib.ptr(y1), _lib.ptr(sc1),
+                _lib.ptr(sh1), _lib.ptr(w2m), _lib.ptr(b2), _lib.ptr(f), _lib.ptr(g), _lib.ptr(arg2), _lib.ptr(gsum)))
+        else:
+            probed_family('embed_gemm', 2.0 * R * c2 * c1, lambda: _lib.call(
+                'pdae_embed_bnrelu_conv_store_groupmax', x, R, c2, c1, _lib.ptr(y1), _lib.ptr(sc1),
+                _lib.ptr(sh1), _lib.ptr(w2m), _lib.ptr(b2), _lib.ptr(f), _lib.ptr(g), _lib.ptr(arg2)))
         # conv3 on concat([g, f]): global half once per group, local half as the GEMM
         wlt = None
         if GLUE and w3m.shape[1] == 2 * c2 and w3m.is_contiguous():
@@ -106,7 +121,6 @@ class PatchEmbedFunction(torch.autograd.Function):
         # conv4: BN2+ReLU producer, only the group max leaves the kernel.  It comes after the
         # last BatchNorm, so it is evaluated only for the groups whose tokens are used
         # (`groups`: the visible patches; masked tokens are discarded by the caller).
-        algebra = groups is not None and masked is not None and masked.numel() > 0 and training
         if groups is not None:
             Gv = groups.numel()
             inv = None
@@ -130,11 +144,11 @@ class PatchEmbedFunction(torch.autograd.Function):
         # masked groups by algebra (backward): needs the complementary list and the per-group bias term
         ctx.algebra = algebra
         if ctx.algebra:
-            ctx.masked, ctx.gb = masked.contiguous(), gb
+            ctx.masked, ctx.gb, ctx.gsum = masked.contiguous(), gb, gsum
         return tok
 
     @staticmethod
-    def _masked_by_algebra(ctx, d3c, S2, f, h3, sc2, sh2, mean2, is2, g2, wl, groups, BG):
+    def _masked_by_algebra(ctx, d3c, S2, f, h3, sc2, sh2, mean2, is2, g2, wl, groups, BG, wg=None, arg2=None):
         """conv3 + BatchNorm-2 backward with the masked groups handled by algebra.  A group whose token is
         dropped sends no activation gradient into BatchNorm-2, so on its rows the conv-output gradient is the
         correction alone, dh_r = u + v * h_r, with h_r = f_r W^T + gb_g (W = the local half of conv3's weight):
@@ -142,7 +156,9 @@ class PatchEmbedFunction(torch.autograd.Function):
             dW    = dW_visible + diag(v) W Gram + xe^T fsum,   Gram = sum f_r^T f_r,  xe_g = u + v * gb_g
             dgb_g = v * (fsum_g W^T) + 32 xe_g,                                     fsum_g = sum_{r in g} f_r
         and the dense sweep + the two R x 512 x 256 GEMMs run on the visible rows only.  Same arithmetic error
-        as the direct form (both 7e-7 of fp64 on a 32 k-row case).  -> dwl, dgb, df, dbeta2, dgamma2."""
+        as the direct form (both 7e-7 of fp64 on a 32 k-row case).  -> dwl, dgb, df, dbeta2, dgamma2.
+        fsum comes from the conv2 forward's epilogue when it left the group sums (ctx.gsum); with wg and arg2 the
+        max-pool gradient dg = dgb wg is added to df where the two products store it (the lists partition the groups)."""
         x = f
         c3, c2 = wl.shape
         masked, gb = ctx.masked, ctx.gb
@@ -155,11 +171,19 @@ class PatchEmbedFunction(torch.autograd.Function):
                   _lib.ptr(groups))              # d3c <- dh of the visible rows; dgb[visible groups] <- their row sums
         u, v = uv[0], uv[1]
         fsum_m = empty((Gm, c2), x)
-        _lib.call('pdae_group_sum_listed', x, Gm, c2, _lib.ptr(f), _lib.ptr(masked), _lib.ptr(fsum_m))
-        if GLUE:                                                      # xe and diag(v) W, one launch
+        gsum = ctx.gsum
+        if gsum is None:
+            _lib.call('pdae_group_sum_listed', x, Gm, c2, _lib.ptr(f), _lib.ptr(masked), _lib.ptr(fsum_m))
+        elif not GLUE:
+            fsum_m = gsum.index_select(0, masked.long())
+        if GLUE:                                                      # xe and diag(v) W (and fsum_m = gsum[masked]), one launch
             xe, wv = empty((Gm, c3), x), empty((c3, c2), x)
-            _lib.call('pdae_embed_masked_prep', x, Gm, c3, c2, _lib.ptr(uv), _lib.ptr(gb), _lib.ptr(masked), _lib.ptr(wl),
-                      _lib.ptr(xe), _lib.ptr(wv))
+            if gsum is None:
+                _lib.call('pdae_embed_masked_prep', x, Gm, c3, c2, _lib.ptr(uv), _lib.ptr(gb), _lib.ptr(masked), _lib.ptr(wl),
+                          _lib.ptr(xe), _lib.ptr(wv))
+            else:
+                _lib.call('pdae_embed_masked_prep_fsum', x, Gm, c3, c2, _lib.ptr(uv), _lib.ptr(gb), _lib.ptr(masked),
+                          _lib.ptr(wl), _lib.ptr(xe), _lib.ptr(wv), _lib.ptr(gsum), _lib.ptr(fsum_m))
         else:
             xe = torch.addcmul(u, gb.index_select(0, masked.long()), v)   # u + v * gb_g  (Gm, 512)
             wv = wl * v.unsqueeze(1)
@@ -180,13 +204,17 @@ class PatchEmbedFunction(torch.autograd.Function):
         (q,), _ = rows_wgrad([wv], [wl], [False])                     # W^T diag(v) W  (symmetric)
         e = rows_gemm(xe, wl, True)                                   # (gb_g * v + u) W   (Gm, 256)
         df = empty((R, c2), x)
-        probed_family('embed_gemm', 2.0 * Rm * c2 * c2, lambda: _lib.call(
-            'pdae_group_gemm_scatter', x, Rm, c2, c2, _lib.ptr(f), _lib.ptr(masked), _lib.ptr(q), _lib.ptr(e),
-            _lib.ptr(df), c2, _lib.ptr(masked)))
         wlt = ctx.wlt if ctx.wlt is not None else wl.t().contiguous()
+        scatter, pool = 'pdae_group_gemm_scatter', ()
+        if wg is not None:
+            dg = rows_gemm(dgb, wg, True)                             # (BG, 256) -> arg-max rows of f, added as df is stored
+            scatter, pool = 'pdae_group_gemm_scatter_add', (_lib.ptr(dg), _lib.ptr(arg2))
+        probed_family('embed_gemm', 2.0 * Rm * c2 * c2, lambda: _lib.call(
+            scatter, x, Rm, c2, c2, _lib.ptr(f), _lib.ptr(masked), _lib.ptr(q), _lib.ptr(e),
+            _lib.ptr(df), c2, _lib.ptr(masked), *pool))
         probed_family('embed_gemm', 2.0 * Rv * c2 * c3, lambda: _lib.call(
-            'pdae_group_gemm_scatter', x, Rv, c2, c3, _lib.ptr(d3c), None, _lib.ptr(wlt), None,
-            _lib.ptr(df), c2, _lib.ptr(groups)))
+            scatter, x, Rv, c2, c3, _lib.ptr(d3c), None, _lib.ptr(wlt), None,
+            _lib.ptr(df), c2, _lib.ptr(groups), *pool))
         return dwl, dgb, df, S2[0], S2[1]
 
     @staticmethod
@@ -208,9 +236,10 @@ class PatchEmbedFunction(torch.autograd.Function):
         # (Rv, 512) grad of relu(bn2(h3)) rows, ReLU-masked, + BatchNorm-2's sums out of the same launch
         d3c, S2 = gemm_bnstats(dy4, w4m, h3, groups, sc2, sh2, mean2, is2)
         del dy4
+        pooled = ctx.algebra and FOLD and 'c' in FOLD_PARTS                           # the max-pool gradient rides in df's two products
         if ctx.algebra:
-            dwl, dgb, df, dbe2, dg2 = PatchEmbedFunction._masked_by_algebra(ctx, d3c, S2, f, h3, sc2, sh2, mean2, is2, g2,
-                                                                             wl, groups, BG)
+            dwl, dgb, df, dbe2, dg2 = PatchEmbedFunction._masked_by_algebra(
+                ctx, d3c, S2, f, h3, sc2, sh2, mean2, is2, g2, wl, groups, BG, *((wg, arg2) if pooled else ()))
             del d3c
         else:
             # ---- ReLU + BN2 backward + per-group sums for the global half
@@ -238,8 +267,9 @@ class PatchEmbedFunction(torch.autograd.Function):
             if isinstance(dwl, tuple):
                 dwl = dwl[0].addcmul_(dwl[1].unsqueeze(1), dwl[2]).add_(dwl[3])
             dw3 = torch.cat([dwg, dwl], dim=1).unsqueeze(-1)
-        dg = rows_gemm(dgb, wg, True)                             # (BG, 256) -> arg-max rows of f
-        _lib.call('pdae_group_scatter_add', x, BG, c2, _lib.ptr(dg), _lib.ptr(arg2), _lib.ptr(df))
+        if not pooled:
+            dg = rows_gemm(dgb, wg, True)                         # (BG, 256) -> arg-max rows of f
+            _lib.call('pdae_group_scatter_add', x, BG, c2, _lib.ptr(dg), _lib.ptr(arg2), _lib.ptr(df))
         # ---- conv2
         dw2, db2 = wgrad_listed(R, df, None, y1, None, sc1, sh1, bias=True)    # db2: column sums of df, same kernel
         d1, S1 = gemm_bnstats(df, w2m, y1, None, sc1, sh1, mean1, is1)      # (R, 128), ReLU-masked, + BatchNorm-1's sums
@@ -247,11 +277,15 @@ class PatchEmbedFunction(torch.autograd.Function):
             DEBUG_KEEP.update(df=df.clone(), d1_pre=d1.clone(), dw2=dw2.clone(), y1=y1.clone())
         del df
         # ---- ReLU + BN1 backward, conv1 (K = 3)
-        _lib.call('pdae_bnrelu_backward_apply', x, BG, c1, _lib.ptr(d1), _lib.ptr(y1), _lib.ptr(sc1), _lib.ptr(sh1),
-                  _lib.ptr(mean1), _lib.ptr(is1), _lib.ptr(g1), _lib.ptr(S1), None, BG, None, None, None)
         dbe1, dg1 = S1[0], S1[1]
         part1 = empty((_lib.lib().pdae_embed_conv1_backward_weight_parts(R), 3, c1), x)
-        _lib.call('pdae_embed_conv1_backward_weight', x, R, c1, _lib.ptr(d1), _lib.ptr(x), _lib.ptr(part1))
+        if FOLD and 'a' in FOLD_PARTS and DEBUG_KEEP is None:         # one pass: d1's BatchNorm-1 backward feeds the weight gradient unstored
+            _lib.call('pdae_embed_bnrelu_backward_conv1_weight', x, R, c1, _lib.ptr(d1), _lib.ptr(y1), _lib.ptr(sc1),
+                      _lib.ptr(sh1), _lib.ptr(mean1), _lib.ptr(is1), _lib.ptr(g1), _lib.ptr(S1), _lib.ptr(x), _lib.ptr(part1))
+        else:
+            _lib.call('pdae_bnrelu_backward_apply', x, BG, c1, _lib.ptr(d1), _lib.ptr(y1), _lib.ptr(sc1), _lib.ptr(sh1),
+                      _lib.ptr(mean1), _lib.ptr(is1), _lib.ptr(g1), _lib.ptr(S1), None, BG, None, None, None)
+            _lib.call('pdae_embed_conv1_backward_weight', x, R, c1, _lib.ptr(d1), _lib.ptr(x), _lib.ptr(part1))
         if GLUE:                                                      # (c1, 3, 1): one pass over d1, ordered partials
             dw1 = empty((c1, 3, 1), x)
             _lib.call('pdae_partials_sum_t', x, part1.shape[0], 3, c1, _lib.ptr(part1), _lib.ptr(dw1))
