@@ -463,7 +463,7 @@ int pdae_rows_gemm(int M, int N, int K, const float* X, const float* W, int w_kn
  *       gsum_by_group), uv[2][C] (nullable) the correction's u, v.  n_listed <= G.
  *   masked_group_sums: dgb[groups[cg]] = v * hs[cg] + 32 * xe[cg]: the row sums of dh over a masked group
  *       (hs = the group's summed conv output without its bias term, xe = u + v * gb).
- *   group_sum_listed: out[cg] = sum of the 32 rows of X's group groups[cg].
+ *   group_sum_listed: out[cg] = sum of the 32 rows of X's group groups[cg] (groups NULL: of group cg, every group).
  *   rows_wgrad_listed (declared with the weight gradients below): dW[N,K] = sum_m dY[rowA(m)]^T X[rowB(m)], whole
  *       32-row groups gathered on either operand; dY = X with one list = a Gram matrix.
  *   group_gemm_scatter: Y[c_groups[m/32]*32 + m%32] = X[a_groups[m/32]*32 + m%32] . W[N,K]^T + gbias[m/32]
@@ -1166,6 +1166,32 @@ int pdae_fewshot_batch(int s, int p, int c, int b, int m, int npoints, const flo
 int pdae_resident_batch(int s, int p, int c, int b, int m, int npoints, const float* set, const int32_t* item,
                         const int32_t* perm /*nullable*/, const int32_t* nmaps /*nullable*/, const float* maps /*(b,3,12)*/,
                         const int32_t* slot /*nullable*/, float* out, int32_t* idx /*nullable*/, pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Input-point gradients (csrc/input_grad.hip; tools/runner_finetune.py:751-833 vis_saliency_map of the reference, which
+ * takes them from framework autograd one cloud at a time).  The two data-only backward steps that end at coordinates.
+ *   group_points_backward  Group.forward's backward: neighbourhood[b,g,j] = xyz[b, knn_idx[b,g,j]] - center[b,g] and
+ *                  center[b,g] = xyz[b, fps_idx[b,g]], so
+ *                    d_xyz[b,n] = sum_{(g,j): knn_idx[b,g,j] == n} d_nbr[b,g,j]
+ *                               + sum_{g: fps_idx[b,g] == n} (d_center[b,g] - sum_j d_nbr[b,g,j]).
+ *                  d_nbr (b,g,k,3), d_center (b,g,3) nullable (= zeros), knn_idx (b,g,k) int64, fps_idx (b,g) int32 ->
+ *                  d_xyz (b,n,3), every element written.  An ORDERED sum, no atomics: one thread owns a point and adds
+ *                  its terms in ascending (g, j), then the centre terms in ascending g, each of them formed as
+ *                  d_center - (the group's d_nbr added in ascending j); a point no index names gets exactly 0.0.  The
+ *                  indices are only compared, never followed: one outside 0..n-1 contributes nothing.  The inverse map
+ *                  is found by scanning the cloud's g*k indices, staged through LDS: n * g * k compares per cloud.
+ *   rows_contract3 dx[row(m)][j] = sum_c d[m][c] * w[c][j], j = 0..2: the data gradient of a Linear / 1x1 conv with
+ *                  three inputs (the embedder's first conv, the position embedding's first layer).  d (m,c) with
+ *                  c % 4 == 0, c <= 1024; w (c,3) as stored (out, in); dx (n_out,3); row_ids (m) int64 nullable:
+ *                  row(m) = row_ids[m] (distinct ids; an id outside 0..n_out-1 writes nothing; rows of dx no id names
+ *                  are left as they were), else m (then n_out must equal m).  32 lanes share a row: lane
+ *                  l adds channels 4l .. 4l+3 (+128, ...) in ascending order, then the lanes meet in a fixed butterfly.
+ * Negative sizes, k or c out of range, a null required pointer: PDAE_ERR_BAD_ARG; more blocks than one launch takes:
+ * PDAE_ERR_UNSUPPORTED; both before anything is launched.  Zero b, n or m: nothing to do.                          */
+int pdae_group_points_backward(int b, int n, int g, int k, const float* d_nbr, const float* d_center /*nullable*/,
+                               const int64_t* knn_idx, const int32_t* fps_idx, float* d_xyz, pdae_stream_t stream);
+int pdae_rows_contract3(int m, int c, const float* d, const float* w, const int64_t* row_ids /*nullable*/, int n_out,
+                        float* dx, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Measurement aids: box calibration for bench.py (csrc/calib.hip). They replace nothing of the reference; the training

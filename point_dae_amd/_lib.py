@@ -151,6 +151,8 @@ _SIGNATURES = {
     "pdae_vote_reduce": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_fewshot_batch": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdae_resident_batch": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_group_points_backward": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_rows_contract3": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp],
     "pdae_calib_mfma_bf16": [_i, _i, _vp, _vp, _vp, _vp],
     "pdae_calib_copy": [ctypes.c_longlong, _vp, _vp, _vp],
 }

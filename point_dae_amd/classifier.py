@@ -36,6 +36,9 @@ class Classifier(nn.Module):
     # None, or why the model cannot train under optimizer.part only_new (runner_finetune.set_bn_eval freezes a part of
     # its BatchNorms): the text of the NotImplementedError runner_finetune raises
     only_new_unsupported = None
+    # whether the eval-mode model can be differentiated with respect to its input points (saliency_ops.input_gradients,
+    # runner_finetune.vis_saliency_map): every link of its backward must carry a data gradient down to (B, N, 3)
+    input_grad_supported = False
 
     # ---- the reference's helpers ------------------------------------------------------------------------------------
     def get_loss_acc(self, ret, gt):

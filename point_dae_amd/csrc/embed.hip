@@ -526,7 +526,7 @@ extern "C" int pdae_group_sum_listed(int n_listed, int C, const float* X, const 
                                      pdae_stream_t stream) {
   if (n_listed < 0 || C <= 0 || C % 4 != 0) return bad_arg("group_sum_listed: C must be a positive multiple of 4");
   if (n_listed == 0) return PDAE_OK;
-  if (!X || !groups || !out) return bad_arg("group_sum_listed: null pointer");
+  if (!X || !out) return bad_arg("group_sum_listed: null pointer");
   const long long n = (long long)n_listed * (C / 4);
   hipLaunchKernelGGL(group_sum_listed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream),
                      n_listed, C / 4, reinterpret_cast<const float4*>(X), groups, reinterpret_cast<float4*>(out));

@@ -3,7 +3,8 @@
 classification fine-tuning runner (--so3_rotation: its rotation-robustness protocol; --svm_classification: the linear-SVM
 evaluation of the frozen encoder; --task_affinity: the linear probe whose test loss ranks corruptions; --vote: a ten-vote
 validation behind a high plain one; --way/--shot/--fold: one fold of few-shot fine-tuning), or with --test --ckpts the
-evaluation of a fine-tuned checkpoint: the plain accuracy, then --vote_rounds rounds of ten-vote evaluation."""
+evaluation of a fine-tuned checkpoint: the plain accuracy, then --vote_rounds rounds of ten-vote evaluation; or with
+--vis_saliency --ckpts its saliency maps: the gradient of the score with respect to every input point of the test set."""
 import torch
 
 from . import dist_utils, parser
@@ -48,6 +49,8 @@ def main(argv=None):
         raise ValueError('--task_affinity runs in one process: --launcher none')
     if args.test and args.launcher != 'none':
         raise NotImplementedError('--test runs in one process: --launcher none')   # runner_finetune.py:697-699
+    if args.vis_saliency and args.launcher != 'none':
+        raise NotImplementedError('--vis_saliency runs in one process: --launcher none')
     if args.launcher == 'none':
         args.distributed = False
         args.world_size = 1
@@ -65,7 +68,7 @@ def main(argv=None):
     if args.max_epoch != -1:
         config.max_epoch = args.max_epoch
     finetune = args.finetune_model or args.scratch_model
-    if not finetune and not args.test and len(config.model['corrupt_type']) == 0:   # main.py:51-55 (pretraining configs only)
+    if not finetune and not args.test and not args.vis_saliency and len(config.model['corrupt_type']) == 0:   # main.py:51-55 (pretraining configs only)
         config.model['corrupt_type'] = config.dataset['train']['others']['corrupt_type']
     assert config.total_bs % args.world_size == 0
     config.dataset.train.others.bs = config.total_bs // args.world_size
@@ -73,6 +76,8 @@ def main(argv=None):
     apply_fewshot_args(args, config)                                                 # main.py:85-91
     if args.test:
         runner_finetune.test_net(args, config)                             # main.py:94-95
+    elif args.vis_saliency:
+        runner_finetune.vis_saliency_map(args, config)                     # main.py:96-97
     elif finetune and args.svm_classification:
         runner_finetune.svm_classification(args, config)                   # main.py:102-103
     elif finetune and args.task_affinity:

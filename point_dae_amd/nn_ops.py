@@ -632,7 +632,10 @@ class _PosEmbed(torch.autograd.Function):
     """Linear(3,128) -> GELU -> Linear(128,C) on centre rows (PointCAE_transformer.py:329-333).
     The first layer (K = 3) with its row gather, GELU and the factor GELU's backward needs is one small kernel
     (pdae_pos_embed_fc1: it also leaves the gathered rows zero-padded to 4 columns, the weight-gradient GEMM's
-    operand); the second layer is a row GEMM.  Centres carry no gradient."""
+    operand); the second layer is a row GEMM.  Centres carry a gradient only in the data-only mode (input-point
+    gradients: they require one and no parameter does): then dz, which the backward forms anyway, is contracted with w1
+    (csrc/input_grad.hip rows_contract3) and lands on the rows `row_ids` name, and the weight gradients are not computed.
+    With a parameter that requires a gradient the backward is what it was: centres carry none."""
 
     @staticmethod
     def forward(ctx, xyz, row_ids, w1, b1, w2, b2):
@@ -642,15 +645,26 @@ class _PosEmbed(torch.autograd.Function):
         _lib.call('pdae_pos_embed_fc1', xyz, M, H, _lib.ptr(xyz), _lib.ptr(row_ids), _lib.ptr(w1.contiguous()), _lib.ptr(b1),
                   _lib.ptr(h), _lib.ptr(gp), _lib.ptr(xp))
         y = rows_gemm(h, w2, False, b2, 0)
-        ctx.save_for_backward(xp, gp, h, w2)
+        ctx.save_for_backward(xp, gp, h, w2, row_ids)
         ctx.sink_tags, ctx.w1 = _sink_tags([w1]), w1
+        ctx.rows_in = xyz.shape[0]
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        xp, gp, h, w2 = ctx.saved_tensors
+        xp, gp, h, w2, row_ids = ctx.saved_tensors
         dy = dy.contiguous()
         dz = rows_gemm(dy, w2, True, None, 3, gp)
+        dxyz = None
+        frozen = not any(ctx.needs_input_grad[2:6])
+        if ctx.needs_input_grad[0] and frozen:           # the data-only mode: with a live parameter centres carry none, as before
+            w1 = ctx.w1.detach().contiguous()
+            # (rows no id names carry no gradient: zeros; the ids of a row list are distinct)
+            dxyz = empty((ctx.rows_in, 3), dy) if row_ids is None else torch.zeros((ctx.rows_in, 3), device=dy.device)
+            _lib.call('pdae_rows_contract3', dz, dz.shape[0], dz.shape[1], _lib.ptr(dz), _lib.ptr(w1), _lib.ptr(row_ids),
+                      ctx.rows_in, _lib.ptr(dxyz))
+        if rows.SKIP_FROZEN_WGRAD and frozen:
+            return dxyz, None, None, None, None, None
         (dw2, dw1p), (db2, db1) = rows_wgrad([dy, dz], [h, xp], [True, True])
         sink = _sink_views(ctx.sink_tags, [ctx.w1])
         if sink:
@@ -659,8 +673,8 @@ class _PosEmbed(torch.autograd.Function):
             owner, idx, views = sink
             owner.sink_strided.append((views[0], dw1p, 3))
             owner.sink_written.update(idx)
-            return None, None, None, db1, dw2, db2
-        return None, None, dw1p[:, :3], db1, dw2, db2
+            return dxyz, None, None, db1, dw2, db2
+        return dxyz, None, dw1p[:, :3], db1, dw2, db2
 
 
 def pos_embed(xyz, seq, rows=None):
@@ -765,6 +779,10 @@ class _TransformerBlock(torch.autograd.Function):
             da0 = dbias_in = None
         # d pos: this block's dx0, or -- summed inside the kernels -- the stack's buffer from its first block
         dpos = None if not ctx.has_pos else (dx0 if dmode == 0 else (dacc if ret_acc else None))
+        if rows.SKIP_FROZEN_WGRAD and not (ctx.needs_input_grad[1] or any(ctx.needs_input_grad[7:17])):
+            # a frozen block differentiated with respect to its input (saliency_ops): no parameter takes a gradient, so
+            # the four weight gradients are not issued (the LayerNorm kernels' parameter sums ride in their launches)
+            return (da0, None, None, dx0, dpos) + (None,) * 20
         sink = _sink_views(ctx.sink_tags, [wqkv, wproj, w1, w2, bf1])   # graphed step: straight into the flat buffer
         if sink:
             # The weight gradients are not needed before the optimiser: the block only QUEUES them (operands kept

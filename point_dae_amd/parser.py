@@ -23,6 +23,10 @@ def get_args(argv=None):
     p.add_argument('--vote', action='store_true', default=False, help='vote acc')
     p.add_argument('--resume', action='store_true', default=False)
     p.add_argument('--test', action='store_true', default=False, help='test mode for certain ckpt')
+    p.add_argument('--vis_saliency', action='store_true', default=False,
+                   help='saliency maps of a fine-tuned checkpoint: input-point gradients over the test set')
+    p.add_argument('--saliency_score', choices=['logit', 'loss'], default='logit',
+                   help='--vis_saliency: differentiate the label\'s logit (the reference) or the cloud\'s cross-entropy')
     p.add_argument('--total_bs', type=int, default=-1)
     p.add_argument('--finetune_model', action='store_true', default=False, help='finetune modelnet with pretrained weight')
     p.add_argument('--scratch_model', action='store_true', default=False, help='training modelnet from scratch')
@@ -48,6 +52,8 @@ def get_args(argv=None):
         raise ValueError('--test and --resume cannot be both activate')
     if args.test and args.ckpts is None:
         raise ValueError('ckpts shouldnt be None while test mode')
+    if args.vis_saliency and args.ckpts is None:
+        raise ValueError('ckpts shouldnt be None while vis_saliency mode')
     if args.vote_rounds < 0:
         raise ValueError('--vote_rounds must not be negative')
     if args.resume and args.start_ckpts is not None:

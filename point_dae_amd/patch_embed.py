@@ -218,8 +218,42 @@ class PatchEmbedFunction(torch.autograd.Function):
         return dwl, dgb, df, S2[0], S2[1]
 
     @staticmethod
+    def _eval_input_grad(ctx, dtok):
+        """The eval-mode, data-only backward: d tokens -> dx (R, 3), no parameter gradient.  On its running estimates a
+        BatchNorm is a per-channel affine map, so its backward is the scale alone, folded into the rows of the weight the
+        gradient meets next (tiny products on weights: sc2 into the two halves of conv3's, sc1 into conv1's); the ReLU
+        masks come out of the same transposed-weight row GEMMs the training backward uses (their BatchNorm sums go
+        unread), and the last step is the 128 -> 3 contraction of csrc/input_grad.hip."""
+        (x, y1, sc1, sh1, mean1, is1, f, g, arg2, h3, sc2, sh2, mean2, is2, arg4,
+         w1m, w2m, wg, wl, w4m, g1, g2, groups, inv) = ctx.saved_tensors
+        R, BG = x.shape[0], x.shape[0] // 32
+        c2, c4 = w2m.shape[0], w4m.shape[0]
+        if groups is not None:
+            raise NotImplementedError('patch embedder: the eval-mode input gradient covers every group (no group list)')
+        dtok = dtok.contiguous()
+        dy4 = empty((R, c4), x)
+        _lib.call('pdae_group_max_scatter', x, BG, c4, _lib.ptr(dtok), _lib.ptr(arg4), _lib.ptr(dy4))
+        d3, _ = gemm_bnstats(dy4, w4m, h3, None, sc2, sh2, mean2, is2)        # (R, 512): d relu(bn2(h3)), ReLU-masked
+        del dy4
+        wls, wgs = wl * sc2.unsqueeze(1), wg * sc2.unsqueeze(1)               # diag(sc2) W: BatchNorm-2's backward
+        df = rows_gemm(d3, wls, True)                                         # (R, 256), the local half
+        dgb = empty((BG, d3.shape[1]), x)
+        _lib.call('pdae_group_sum_listed', x, BG, d3.shape[1], _lib.ptr(d3), None, _lib.ptr(dgb))
+        del d3
+        dg = rows_gemm(dgb, wgs, True)                                        # (BG, 256) -> the arg-max rows of f
+        _lib.call('pdae_group_scatter_add', x, BG, c2, _lib.ptr(dg), _lib.ptr(arg2), _lib.ptr(df))
+        d1, _ = gemm_bnstats(df, w2m, y1, None, sc1, sh1, mean1, is1)         # (R, 128): d relu(bn1(y1)), ReLU-masked
+        del df
+        w1s = (w1m * sc1.unsqueeze(1)).contiguous()                           # (128, 3): BatchNorm-1's backward
+        dx = empty((R, 3), x)
+        _lib.call('pdae_rows_contract3', x, R, d1.shape[1], _lib.ptr(d1), _lib.ptr(w1s), None, R, _lib.ptr(dx))
+        return (dx,) + (None,) * 17
+
+    @staticmethod
     def backward(ctx, dtok):
         if not ctx.training:
+            if ctx.needs_input_grad[0] and not any(ctx.needs_input_grad[1:13]):
+                return PatchEmbedFunction._eval_input_grad(ctx, dtok)
             raise NotImplementedError('patch embedder backward is implemented for training-mode BatchNorm')
         (x, y1, sc1, sh1, mean1, is1, f, g, arg2, h3, sc2, sh2, mean2, is2, arg4,
          w1m, w2m, wg, wl, w4m, g1, g2, groups, inv) = ctx.saved_tensors
@@ -305,6 +339,14 @@ def patch_embed(points, first_conv, second_conv, training, groups=None, masked=N
     list (the groups whose tokens the caller drops): their share of the backward is then
     done by algebra (PatchEmbedFunction._masked_by_algebra)."""
     BG, n, _ = points.shape
+    if points.requires_grad and torch.is_grad_enabled():
+        # input-point gradients: the fused path's eval-mode data-only backward (PatchEmbedFunction._eval_input_grad)
+        if n != 32:
+            raise NotImplementedError('patch embedder: a gradient with respect to the points needs group_size == 32 '
+                                      '(the fused path), got %d' % n)
+        if isinstance(first_conv[1], torch.nn.SyncBatchNorm) or isinstance(second_conv[1], torch.nn.SyncBatchNorm):
+            raise NotImplementedError('patch embedder: a gradient with respect to the points is not implemented under '
+                                      'SyncBatchNorm (the fused path keeps plain BatchNorm1d)')
     if n != 32:
         # the fused kernels tile a patch as one 32-row MFMA tile; other group sizes of the reference's YAML grid
         # (16, 64) take the layer-by-layer path on the same row GEMMs

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import nn_ops
+from . import _lib, nn_ops
 from .arena import arena, begin_step
 from .chamfer_dist import ChamferDistanceL1, ChamferDistanceL2
 from .corrupt_util_tensor import corrupt_patches, draw_corruption
@@ -36,6 +36,36 @@ def trunc_normal_(tensor, mean=0., std=1., a=-2., b=2.):
     return nn.init.trunc_normal_(tensor, mean=mean, std=std, a=a, b=b)
 
 
+class _GroupPoints(torch.autograd.Function):
+    """Group.forward for a cloud that requires a gradient: the same two launches, and a backward of one launch
+    (csrc/input_grad.hip group_points_backward: an ordered sum per point, no atomics).  The selection of centres and
+    neighbours is piecewise constant in xyz: the gradient flows through the gathers and the centre subtraction only."""
+
+    @staticmethod
+    def forward(ctx, xyz, num_group, group_size):
+        fps_idx, center = furthest_point_sample_with_centres(xyz, num_group)
+        _, knn_idx, neighborhood = knn(xyz, center, group_size, with_neighbourhood=True)
+        ctx.save_for_backward(fps_idx, knn_idx)
+        ctx.N = xyz.shape[1]
+        ctx.mark_non_differentiable(fps_idx, knn_idx)
+        ctx.set_materialize_grads(False)
+        return neighborhood, center, fps_idx, knn_idx
+
+    @staticmethod
+    def backward(ctx, d_nbr, d_center, _dfps, _dknn):
+        fps_idx, knn_idx = ctx.saved_tensors
+        B, G, k = knn_idx.shape
+        like = d_nbr if d_nbr is not None else d_center
+        if like is None:
+            return None, None, None
+        d_nbr = d_nbr.contiguous() if d_nbr is not None else torch.zeros((B, G, k, 3), device=like.device)
+        d_center = d_center.contiguous() if d_center is not None else None
+        d_xyz = torch.empty((B, ctx.N, 3), dtype=torch.float32, device=like.device)
+        _lib.call('pdae_group_points_backward', d_nbr, B, ctx.N, G, k, _lib.ptr(d_nbr), _lib.ptr(d_center),
+                  _lib.ptr(knn_idx), _lib.ptr(fps_idx), _lib.ptr(d_xyz))
+        return d_xyz, None, None
+
+
 class Group(nn.Module):
     """FPS centres + kNN patches, centre-subtracted (Group.forward :61-86)."""
 
@@ -43,10 +73,18 @@ class Group(nn.Module):
         super().__init__()
         self.num_group, self.group_size = num_group, group_size
 
-    @torch.no_grad()
-    def forward(self, xyz):
-        _, center = furthest_point_sample_with_centres(xyz, self.num_group)
-        _, _, neighborhood = knn(xyz, center, self.group_size, with_neighbourhood=True)
+    def forward(self, xyz, indices=None):
+        """-> neighbourhood (B,G,k,3), centres (B,G,3).  No gradient, like the reference's extension ops -- unless xyz
+        requires one (input-point gradients: saliency_ops), then through _GroupPoints with the same forward launches.
+        indices: a dict that receives fps_idx (B,G) int32 and knn_idx (B,G,k) int64."""
+        if torch.is_grad_enabled() and xyz.requires_grad:
+            neighborhood, center, fps_idx, knn_idx = _GroupPoints.apply(xyz, self.num_group, self.group_size)
+        else:
+            with torch.no_grad():
+                fps_idx, center = furthest_point_sample_with_centres(xyz, self.num_group)
+                _, knn_idx, neighborhood = knn(xyz, center, self.group_size, with_neighbourhood=True)
+        if indices is not None:
+            indices.update(fps_idx=fps_idx, knn_idx=knn_idx)
         return neighborhood, center
 
 

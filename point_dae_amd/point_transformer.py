@@ -31,6 +31,8 @@ class _TransformerClassifier(Classifier):
     """The trunk both classifiers share; a subclass gives build_head() -> cls_head_finetune."""
     # parameters whose gradients backward produces last (FlatDataParallel lays them at the end of the flat buffer)
     late_grad_prefixes = ('encoder.',)
+    # grouping, the position embedding and the eval-mode patch embedder carry a gradient down to the points
+    input_grad_supported = True
 
     def __init__(self, config, **kwargs):
         super().__init__()
@@ -67,9 +69,15 @@ class _TransformerClassifier(Classifier):
         B = pts.shape[0]
         G, C = self.num_group, self.trans_dim
         T = G + 1
-        neighborhood, center = self.group_divider(pts)
+        neighborhood, center = self.group_divider(pts, capture)      # (capture also receives fps_idx, knn_idx)
         tokens = self.encoder(neighborhood)                                           # (B, G, C), every group
         pos = nn_ops.pos_embed(center.reshape(B * G, 3), self.pos_embed).reshape(B, G, C)
+        return self.trunk_from_tokens(tokens, pos, center, capture)
+
+    def trunk_from_tokens(self, tokens, pos, center=None, capture=None):
+        """tokens (B, G, C), their position embedding (B, G, C) -> the pooled feature (B, 2C)."""
+        B, G, C = tokens.shape
+        T = G + 1
         x = finetune_ops.prepend_token(tokens, self.cls_token).reshape(B * T, C)
         pos = finetune_ops.prepend_token(pos, self.cls_pos).reshape(B * T, C)
         x = self.blocks(x, pos, B, T)                    # nn_ops.Pending: the final norm's kernel adds the last branch

@@ -57,6 +57,11 @@ class _Pad2d(torch.autograd.Function):
 
 PAD2D = os.environ.get('PDAE_PAD2D', os.environ.get('PDAE_GLUE', '1')) != '0'
 
+# A backward whose parameter inputs all have requires_grad == False (a frozen model differentiated with respect to its
+# input: saliency_ops) skips its weight-gradient launches.  (A/B: 0 = they are issued anyway, as before; with any
+# parameter requiring a gradient the switch changes nothing)
+SKIP_FROZEN_WGRAD = os.environ.get('PDAE_SKIP_FROZEN_WGRAD', '1') != '0'
+
 
 def pad2d(x, pr, pc):
     """zero rows below / zero columns right of a 1-D or 2-D fp32 device tensor (1-D: pc elements appended)."""
@@ -295,6 +300,8 @@ class _Linear(torch.autograd.Function):
         if ctx.relu:
             dy = dy * (y > 0)
         dx = rows_gemm(dy, w, True) if ctx.needs_input_grad[0] else None
+        if SKIP_FROZEN_WGRAD and not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return dx, None, None, None
         dws, dbs = rows_wgrad([dy], [x], [ctx.has_bias])
         return dx, dws[0], dbs[0], None
 

@@ -20,6 +20,9 @@ checkpoint by voting: per test cloud ten subsets of its FPS order, each through 
 the logits.  vote_pass runs one such pass on vote_ops (csrc/vote.hip); FPS is kept per test batch across passes, the hits
 are counted on the device and test_net reads its rounds' counters once.
 
+vis_saliency_map (:751-833, main.py --vis_saliency) differentiates a fine-tuned classifier's score with respect to its
+input points over the test set, a batch at a time (saliency_ops), and saves the reference's (n, npoints, 6) tensor.
+
 Few-shot fine-tuning (main.py --way/--shot/--fold, datasets.ModelNetFewShot) is run_net on one resident episode: the
 train loader yields the draws of a batch (items, a fresh point shuffle per row) and fewshot_train_points makes the step's
 input of them -- fewshot_ops (csrc/fewshot.hip): one launch --; the test loader's FPS-to-npoints point sets are taken once
@@ -307,6 +310,51 @@ def test_net(args, config, log=print):
         acc = max(accs)
     log('[TEST_VOTE] acc = %.4f' % acc)
     return acc
+
+
+def vis_saliency_map(args, config, log=print):
+    """runner_finetune.py:751-833 (main.py --vis_saliency): the gradient of a fine-tuned classifier's score with respect
+    to every input point, over the whole test set.  The test loader and the model as in test_net; every parameter frozen;
+    per test batch -- the full total_bs, where the reference takes one cloud at a time because its `logits[0, label]`
+    must be a scalar -- FPS to npoints and saliency_ops.input_gradients (one eval forward, one data-only backward);
+    cat([points, grad], dim=2) of all batches, (n, npoints, 6) on the device, is saved ONCE to
+    <experiment_path>/saliency.pt (the reference's tensor layout; its hard-coded path and debugger stop are not
+    reproduced).  '[TEST] acc' comes from the same logits.  Must not run under no_grad.  -> the saved tensor."""
+    import os
+    from . import saliency_ops
+    if getattr(args, 'distributed', False) or getattr(args, 'launcher', 'none') != 'none':
+        raise NotImplementedError('--vis_saliency runs in one process: --launcher none')
+    device = torch.device('cuda', torch.cuda.current_device())
+    log('Saliency start ... ')
+    test_loader = _loader(config.dataset.test, device, args.seed, 0, 1, config.total_bs)
+    _log_sources(log, None, test_loader)
+    base_model = builder.model_builder(config.model)
+    if not getattr(base_model, 'input_grad_supported', False):
+        raise NotImplementedError(
+            '--vis_saliency: %s.input_grad_supported is False -- its backward carries no gradient down to the input '
+            'points (the PointTransformer classifiers do)' % type(base_model).__name__)
+    builder.load_model(base_model, args.ckpts)
+    base_model = base_model.to(device).eval()
+    for p in base_model.parameters():
+        p.requires_grad_(False)
+    score = getattr(args, 'saliency_score', 'logit')
+    log('Saliency backend: %s, score: %s' % (saliency_ops.backend(), score))
+    maps, preds, labels = [], [], []
+    for _, _, data in test_loader:
+        points, label = data[0].cuda(), data[1].cuda().view(-1).long()
+        with torch.no_grad():
+            _, points = fps(points, config.npoints)
+        logits, grad = saliency_ops.input_gradients(base_model, points, label, score)
+        maps.append(torch.cat([points[:, :, :3], grad], dim=2))
+        preds.append(logits.argmax(-1).view(-1))
+        labels.append(label)
+    saliency = torch.cat(maps)
+    pred, label = torch.cat(preds), torch.cat(labels)
+    log('[TEST] acc = %.4f' % _percent((pred == label).sum().item(), label.numel()))
+    path = os.path.join(args.experiment_path, 'saliency.pt')
+    torch.save(saliency, path)
+    log('Saliency map %s saved to %s' % (tuple(saliency.shape), path))
+    return saliency
 
 
 def _loader(node, device, seed, rank, world, bs, steps_per_epoch=None):
