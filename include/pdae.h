@@ -128,7 +128,8 @@ int pdae_resample_affine(int b, int p, int c, int point_all, int npoints, const 
 /* query_ball_point_kernel_wrapper(b, n, m, radius, nsample, new_xyz, xyz, idx)
  *   ball_query_gpu.cu:49-57 (kernel :12-47), host ball_query.cpp:11-35.
  * idx (b,m,nsample) i32: first nsample indices k (ascending) with d2 < r*r;
- * short lists padded with the first hit; empty ball -> zeros.              */
+ * short lists padded with the first hit; empty ball -> zeros.  n == 0 (xyz
+ * may then be NULL) leaves every ball empty.                               */
 int pdae_ball_query(int b, int n, int m, float radius, int nsample,
                     const float* new_xyz, const float* xyz, int32_t* idx,
                     pdae_stream_t stream);

@@ -231,7 +231,7 @@ extern "C" int pdae_ball_query(int b, int n, int m, float radius, int nsample,
   using namespace pdae;
   if (b < 0 || n < 0 || m < 0 || nsample < 0) return bad_arg("ball_query: negative size");
   if (b == 0 || m == 0 || nsample == 0) return PDAE_OK;
-  if (!new_xyz || !xyz || !idx) return bad_arg("ball_query: null pointer");
+  if (!new_xyz || !idx || (n > 0 && !xyz)) return bad_arg("ball_query: null pointer");  // an empty cloud has no storage
   if (b > 65535) return unsupported("ball_query: b > 65535");
   const size_t lds = (size_t)n * 3 * sizeof(float);
   if (lds > 150 * 1024) return unsupported("ball_query: n > 12800 not implemented");

@@ -35,9 +35,11 @@ def _fps_definition(p, m):
     return np.array(out, np.int32)
 
 
-@pytest.mark.parametrize("N,m", [(1024, 64), (1024, 512), (512, 128), (2048, 128), (100, 17)])
+@pytest.mark.parametrize("N,m", [(1024, 64), (1024, 512), (512, 128), (2048, 128), (100, 17),
+                                 # the ranges tests/test_gpu_ops_forms.py leans on the oracle in: 9, 33 and 64 columns
+                                 (4097, 16), (16385, 12), (32768, 12)])
 def test_fps_matches_definition(oracle_ops, N, m):
-    x = make_clouds(1, 3, N, "shapes" if N >= 512 else "uniform")
+    x = make_clouds(1, 3, N, "shapes" if 512 <= N <= 2048 else "uniform")
     idx, ctr = oracle_ops.furthest_point_sample(x, m, return_centres=True)
     for b in range(x.shape[0]):
         np.testing.assert_array_equal(idx[b], _fps_definition(x[b], m))
@@ -100,9 +102,10 @@ def test_opt_n_threads(oracle_ops):
 
 
 # ------------------------------------------------------------------ kNN ----
-@pytest.mark.parametrize("N,G,k", [(1024, 64, 32), (2048, 128, 32), (77, 9, 5), (40, 3, 40)])
+@pytest.mark.parametrize("N,G,k", [(1024, 64, 32), (2048, 128, 32), (77, 9, 5), (40, 3, 40),
+                                   (2049, 7, 64), (65, 7, 1)])       # sizes of tests/test_gpu_ops_forms.py
 def test_knn_matches_stable_sort(oracle_ops, N, G, k):
-    x = make_clouds(3, 2, N, "shapes" if N >= 512 else "uniform")
+    x = make_clouds(3, 2, N, "shapes" if 512 <= N <= 2048 else "uniform")
     ctr = x[:, :G].copy()
     dist, idx, nbr = oracle_ops.knn(x, ctr, k, return_nbr=True)
     assert idx.dtype == np.int64 and idx.shape == (2, G, k)
@@ -136,9 +139,10 @@ def _ball_definition(xyz, new_xyz, r, ns):
     return out
 
 
-@pytest.mark.parametrize("N,m,r,ns", [(1024, 512, 0.2, 32), (512, 128, 0.4, 64), (100, 7, 0.05, 8)])
+@pytest.mark.parametrize("N,m,r,ns", [(1024, 512, 0.2, 32), (512, 128, 0.4, 64), (100, 7, 0.05, 8),
+                                      (5462, 9, 0.3, 100), (12800, 9, 0.3, 16), (1, 9, 0.3, 16)])   # test_gpu_ops_forms.py
 def test_ball_query_matches_definition(oracle_ops, N, m, r, ns):
-    x = make_clouds(5, 2, N, "shapes" if N >= 512 else "uniform")
+    x = make_clouds(5, 2, N, "shapes" if 512 <= N <= 2048 else "uniform")
     new_xyz = x[:, :m].copy()
     new_xyz[0, 0] = [5, 5, 5]          # empty ball -> zeros
     idx = oracle_ops.ball_query(r, ns, x, new_xyz)
@@ -308,3 +312,24 @@ def test_three_nn_and_interpolate_against_definitions(oracle_ops):
     # fewer than three known points: +inf and index 0 in the unused slots
     d2s, idxs = oracle_ops.three_nn(unknown[:, :5], known[:, :2])
     assert np.isinf(d2s[..., 2]).all() and (idxs[..., 2] == 0).all()
+
+
+@pytest.mark.parametrize('m,n', [(1025, 257), (2049, 255), (2, 1)])
+def test_three_nn_matches_definition_at_the_tile_sizes(oracle_ops, m, n):
+    """The known-point counts tests/test_gpu_ops_forms.py relies on the oracle for (past the kernel's 1024-point tile),
+    with a duplicated known point whose copies lie 1024 or more indices apart."""
+    rng = np.random.default_rng(m)
+    unknown = rng.uniform(-1, 1, (2, n, 3)).astype(np.float32)
+    known = rng.uniform(-1, 1, (2, m, 3)).astype(np.float32)
+    known[:, m - 1] = known[:, 0]
+    unknown[:, 0] = known[:, 0]
+    d2, idx = oracle_ops.three_nn(unknown, known)
+    diff = unknown[:, :, None, :] - known[:, None, :, :]
+    full = (diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]) + diff[..., 2] * diff[..., 2]
+    order = np.argsort(full, axis=2, kind='stable')[:, :, :3]
+    k = min(m, 3)
+    assert np.array_equal(idx[..., :k], order[..., :k].astype(np.int32))
+    assert np.array_equal(d2[..., :k], np.take_along_axis(full, order, 2)[..., :k])
+    assert (idx[:, 0, 0] == 0).all() and (idx[:, 0, 1] == m - 1).all() and (d2[:, 0, :2] == 0).all()
+    if m < 3:
+        assert np.isinf(d2[..., m:]).all() and (idx[..., m:] == 0).all()
