@@ -11,6 +11,17 @@
 //   rowscale            da = keep[b] * dy                (its backward)
 //   colsum              bias gradients
 // One wave per row for the LayerNorm kernels (C <= 2048), float4 everywhere.
+// The two LayerNorm kernels and tail_rows_scatter exist in two forms.  The *_legacy_kernel ones are the first
+// versions: the forward walks its column slots one after the other and, per slot, a runtime slab loop with a full
+// wait per trip (about eight dependent trips to memory per row at C = 384 and three slabs); the backward and the
+// scatter read through `on ? *ptr : zero4`, which hipcc compiles as a select between the address and a stack slot:
+// flat 4-byte loads, a private segment, again a slab loop with a full wait per trip.  The forms without the suffix
+// (the default) instantiate the slot count, the slab count and the presence flags and issue every load of a row
+// -- as guarded 16-byte global loads -- before the first use: one trip per row, the same operations in the same
+// order, the same bits.  PDAE_LN=0 launches the legacy forms (A/B handle and the tests' reference: ln_form()).
+#include <stdlib.h>
+#include <string.h>
+
 #include "common.h"
 
 namespace pdae {
@@ -25,7 +36,7 @@ constexpr int LN_MAX4 = 8;  // float4 per lane: C <= 2048
 
 // s = x (+ keep[row/T] * (br + bias): the previous sub-layer's branch, i.e. scale_residual)
 //       (+ pos);  y = LN(s).  s is written to xsum whenever it differs from x.
-__global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(
+__global__ __launch_bounds__(256) void add_layernorm_fwd_legacy_kernel(
     int M, int C, const float* __restrict__ x, const float* __restrict__ pos,
     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
     float* __restrict__ xsum, float* __restrict__ y, float* __restrict__ mean,
@@ -98,17 +109,114 @@ __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(
   }
 }
 
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void add4(float4& a, const float4& b) { a.x += b.x, a.y += b.y, a.z += b.z, a.w += b.w; }
+
+// The same sweep with ONE trip to memory per row: the column slots NS, the slab count and the presence of bias / pos are
+// compile-time, so every load of the row -- x, all slabs of the branch, bias, pos, gamma, beta, keep -- is issued back
+// to back before the first use, and the arithmetic that follows waits on counted vmcnt only.  Same operations per
+// element in the same order as the form above: slabs in slab order, + bias, * keep, x + t, + pos.
+// SLABS: 0 = no branch, 1..4 = that many slabs, -1 = br_slabs of them: slab 0 up front, then one load per slot and trip.
+template <int NS, int SLABS, bool BIAS, bool POS>
+__global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(
+    int M, int C, const float* __restrict__ x, const float* __restrict__ pos,
+    const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+    float* __restrict__ xsum, float* __restrict__ y, float* __restrict__ mean,
+    float* __restrict__ rstd, const float* __restrict__ br, const float* __restrict__ bias,
+    const float* __restrict__ keep, int T, int br_slabs) {
+  constexpr bool BR = SLABS != 0;
+  constexpr int SL = SLABS > 0 ? SLABS : 1;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int lane = lane_id();
+  const int n4 = C >> 2;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float k = 1.f;
+  if (keep) k = keep[row / T];
+  float4 v[NS], u[SL][NS], bb[NS], pp[NS], g[NS], be[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    v[i] = bb[i] = pp[i] = g[i] = be[i] = zero4;
+#pragma unroll
+    for (int q = 0; q < SL; ++q) u[q][i] = zero4;
+    const int c4 = lane + i * kWave;
+    if (c4 < n4) {
+      const size_t off = (size_t)row * C + c4 * 4;
+      v[i] = ld4(x + off);
+      if (BR) {
+#pragma unroll
+        for (int q = 0; q < SL; ++q) u[q][i] = ld4(br + (size_t)q * M * C + off);
+      }
+      if (POS) pp[i] = ld4(pos + off);
+      if (BR && BIAS) bb[i] = ld4(bias + c4 * 4);
+      g[i] = ld4(gamma + c4 * 4);
+      be[i] = ld4(beta + c4 * 4);
+    }
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const int c4 = lane + i * kWave;
+    if (c4 < n4) {
+      float4 a = v[i];
+      if (BR) {      // same operation order as scale_residual: res + keep * (a + bias)
+        float4 t = u[0][i];
+#pragma unroll
+        for (int q = 1; q < SL; ++q) add4(t, u[q][i]);
+        if (SLABS < 0) {
+          for (int q = 1; q < br_slabs; ++q) add4(t, ld4(br + ((size_t)q * M + row) * C + c4 * 4));
+        }
+        if (BIAS) add4(t, bb[i]);
+        if (keep) t.x *= k, t.y *= k, t.z *= k, t.w *= k;
+        add4(a, t);
+      }
+      if (POS) add4(a, pp[i]);
+      if (POS || BR) store_wt4(xsum + (size_t)row * C + c4 * 4, a);
+      v[i] = a;
+      s += (a.x + a.y) + (a.z + a.w);
+    }
+  }
+  const float mu = wave_sum(s) / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const int c4 = lane + i * kWave;
+    if (c4 < n4) {
+      const float dx = v[i].x - mu, dy = v[i].y - mu, dz = v[i].z - mu, dw = v[i].w - mu;
+      q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    }
+  }
+  const float rs = rsqrtf(wave_sum(q) / (float)C + eps);
+  if (lane == 0) {
+    mean[row] = mu;
+    rstd[row] = rs;
+  }
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const int c4 = lane + i * kWave;
+    if (c4 < n4) {
+      float4 o;
+      o.x = (v[i].x - mu) * rs * g[i].x + be[i].x;
+      o.y = (v[i].y - mu) * rs * g[i].y + be[i].y;
+      o.z = (v[i].z - mu) * rs * g[i].z + be[i].z;
+      o.w = (v[i].w - mu) * rs * g[i].w + be[i].w;
+      store_wt4(y + (size_t)row * C + c4 * 4, o);
+    }
+  }
+}
+
 // dx = rstd * (g*dy - mean(g*dy) - xhat * mean(g*dy*xhat)) (+ dres);
 // dgamma += sum dy*xhat, dbeta += sum dy over this block's rows (LDS, then atomics).
 // One wave per row, NS float4 slots per lane (C <= 256*NS), NW waves per block, `rows`
 // rows per block (a multiple of NW).  The pass is latency-bound, not bandwidth-bound
-// (12-50 MB per launch): every load of a row -- dy, x, the skip gradient -- is issued
-// before the first reduction and gamma stays in registers across rows.  The 2*C global
+// (12-50 MB per launch); gamma stays in registers across rows.  (This legacy form was MEANT to
+// issue every load of a row before the first reduction; as compiled it does not -- see the head
+// of this file and layernorm_bwd_kernel below.)  The 2*C global
 // atomics per BLOCK are what the launch pays for (device-scope float atomics run at
 // ~28 G/s on 24 cache lines: 2048 blocks cost 55 us, 128 blocks 3 us), hence 16-wave
 // blocks: few blocks, many rows in flight per CU.
 template <int NS, int NW>
-__global__ __launch_bounds__(NW * 64) void layernorm_bwd_kernel(
+__global__ __launch_bounds__(NW * 64) void layernorm_bwd_legacy_kernel(
     int M, int C, int rows, const float* __restrict__ dy, const float* __restrict__ x,
     const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ gamma, const float* __restrict__ dres, float* __restrict__ dx,
@@ -191,6 +299,146 @@ __global__ __launch_bounds__(NW * 64) void layernorm_bwd_kernel(
         } else if (dacc_mode == 2) {
           float4 t = *reinterpret_cast<const float4*>(dacc + (size_t)row * C + c4 * 4);
           t.x += o.x, t.y += o.y, t.z += o.z, t.w += o.w;
+          *reinterpret_cast<float4*>(dacc + (size_t)row * C + c4 * 4) = t;
+        }
+        if (dbias) {
+          if (keep) o.x *= kp_, o.y *= kp_, o.z *= kp_, o.w *= kp_;
+          if (da) store_wt4(da + (size_t)row * C + c4 * 4, o);
+          ac[i].x += o.x, ac[i].y += o.y, ac[i].z += o.z, ac[i].w += o.w;
+        }
+      }
+    }
+  }
+  const int nred = dbias ? 3 : 2;
+  float* mine = red + (size_t)w * nred * C;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const int c4 = lane + i * kWave;
+    if (c4 < n4) {
+      *reinterpret_cast<float4*>(mine + c4 * 4) = ag[i];
+      *reinterpret_cast<float4*>(mine + C + c4 * 4) = ab[i];
+      if (dbias) *reinterpret_cast<float4*>(mine + 2 * C + c4 * 4) = ac[i];
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < nred * C; c += NW * 64) {
+    float t = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < NW; ++k) t += red[(size_t)k * nred * C + c];
+    col_add(c < C ? dgamma + c : (c < 2 * C ? dbeta + (c - C) : dbias + (c - 2 * C)), part, blockIdx.x,
+            nred * C, c, t);
+  }
+}
+
+// The same kernel with one trip to memory per row.  Guarded 16-byte loads (`if (on) v = *p` on a zeroed value: the
+// `on ? *p : zero4` above is a conditional LVALUE, i.e. a select between the address and a stack slot holding the zero,
+// read with flat loads) and a compile-time slab count: issue() starts every load of a row -- all slabs of dy, x, the
+// skip gradient, mean, rstd, keep -- and leaves the values raw; the slabs are added up where the row is consumed, so
+// nothing waits inside issue().  The old dacc value (dacc_mode 2) is loaded at the head of its row, before the
+// reductions.  With more than one row per wave (RPW != 1) the next row's issue() runs before the current row's
+// reductions.  Rows, NW, the grid, the LDS slots, the order in which a wave adds its rows and the column pass are those
+// of the form above, and so is every operation on an element: the results are the same bits.
+// SLABS: 1..4 = that many slabs, -1 = dy_slabs of them: slab 0 with the row, then one load per slot and trip at the use.
+// RPW: rows per wave, 1 or 2; 0 = rows / NW of them.  DRES: the skip gradient is given.
+template <int NS, int NW, int SLABS, int RPW, bool DRES>
+__global__ __launch_bounds__(NW * 64) void layernorm_bwd_kernel(
+    int M, int C, int rows, const float* __restrict__ dy, const float* __restrict__ x,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ gamma, const float* __restrict__ dres, float* __restrict__ dx,
+    float* __restrict__ dgamma, float* __restrict__ dbeta, const float* __restrict__ keep, int T,
+    float* __restrict__ da, float* __restrict__ dbias, int dy_slabs, float* __restrict__ dacc, int dacc_mode,
+    float* __restrict__ part) {
+  constexpr int SL = SLABS > 0 ? SLABS : 1;
+  extern __shared__ float red[];  // [NW][3][C]: one plain-store slot per wave
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const int n4 = C >> 2;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 ag[NS], ab[NS], g[NS], ac[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    ag[i] = ab[i] = ac[i] = g[i] = zero4;
+    const int c4 = lane + i * kWave;
+    if (c4 < n4) g[i] = ld4(gamma + c4 * 4);
+  }
+  float4 u[SL][NS], xv[NS], e[NS];
+  float mu = 0.f, rs = 0.f, kp = 1.f;
+  auto issue = [&](int row) {
+    mu = 0.f, rs = 0.f, kp = 1.f;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      xv[i] = e[i] = zero4;
+#pragma unroll
+      for (int q = 0; q < SL; ++q) u[q][i] = zero4;
+    }
+    if (row < M) {
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const int c4 = lane + i * kWave;
+        if (c4 < n4) {
+          const size_t off = (size_t)row * C + c4 * 4;
+#pragma unroll
+          for (int q = 0; q < SL; ++q) u[q][i] = ld4(dy + (size_t)q * M * C + off);
+          xv[i] = ld4(x + off);
+          if (DRES) e[i] = ld4(dres + off);     // (compile-time: as a uniform branch it is compiled with a full wait behind it)
+        }
+      }
+      mu = mean[row];
+      rs = rstd[row];
+      if (keep) kp = keep[row / T];
+    }
+  };
+  const int row0 = blockIdx.x * rows + w;
+  const int nrr = RPW ? RPW : rows / NW;
+  issue(row0);
+  for (int rr = 0; rr < nrr; ++rr) {
+    const int row = row0 + rr * NW;
+    if (row >= M) break;
+    float4 old[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      old[i] = zero4;
+      const int c4 = lane + i * kWave;
+      if (dacc_mode == 2 && c4 < n4) old[i] = ld4(dacc + (size_t)row * C + c4 * 4);
+    }
+    float4 gd[NS], xh[NS], sk[NS];
+    float s1 = 0.f, s2 = 0.f;
+    const float rs_ = rs, kp_ = kp;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      float4 d = u[0][i];
+#pragma unroll
+      for (int q = 1; q < SL; ++q) add4(d, u[q][i]);
+      if (SLABS < 0) {
+        const int c4 = lane + i * kWave;
+        if (c4 < n4)
+          for (int q = 1; q < dy_slabs; ++q) add4(d, ld4(dy + ((size_t)q * M + row) * C + c4 * 4));
+      }
+      // (slots past the row hold zeros: xh = -mu*rs there, but d = gd = 0 keeps every sum exact)
+      xh[i] = make_float4((xv[i].x - mu) * rs, (xv[i].y - mu) * rs, (xv[i].z - mu) * rs, (xv[i].w - mu) * rs);
+      gd[i] = make_float4(d.x * g[i].x, d.y * g[i].y, d.z * g[i].z, d.w * g[i].w);
+      s1 += (gd[i].x + gd[i].y) + (gd[i].z + gd[i].w);
+      s2 += (gd[i].x * xh[i].x + gd[i].y * xh[i].y) + (gd[i].z * xh[i].z + gd[i].w * xh[i].w);
+      ag[i].x += d.x * xh[i].x, ag[i].y += d.y * xh[i].y, ag[i].z += d.z * xh[i].z, ag[i].w += d.w * xh[i].w;
+      ab[i].x += d.x, ab[i].y += d.y, ab[i].z += d.z, ab[i].w += d.w;
+      sk[i] = e[i];
+    }
+    if (RPW != 1 && rr + 1 < nrr) issue(row + NW);      // the next row's loads fly during the reductions
+    const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int c4 = lane + i * kWave;
+      if (c4 < n4) {
+        float4 o;
+        o.x = rs_ * (gd[i].x - m1 - xh[i].x * m2) + sk[i].x;
+        o.y = rs_ * (gd[i].y - m1 - xh[i].y * m2) + sk[i].y;
+        o.z = rs_ * (gd[i].z - m1 - xh[i].z * m2) + sk[i].z;
+        o.w = rs_ * (gd[i].w - m1 - xh[i].w * m2) + sk[i].w;
+        store_wt4(dx + (size_t)row * C + c4 * 4, o);
+        if (dacc_mode == 1) {
+          store_wt4(dacc + (size_t)row * C + c4 * 4, o);
+        } else if (dacc_mode == 2) {
+          float4 t = old[i];
+          add4(t, o);
           *reinterpret_cast<float4*>(dacc + (size_t)row * C + c4 * 4) = t;
         }
         if (dbias) {
@@ -401,6 +649,73 @@ static int cs_rows(int M) {
   return rows;
 }
 
+// PDAE_LN (A/B handle, read once; to be retired once settled -- tools/lab/NOTES.md): unset or 1 = the one-trip
+// LayerNorm kernels and the guarded tail_rows_scatter, 0 = the *_legacy_kernel forms, f / b = the forward / the
+// backward alone in the new form (bit 0: forward, bit 1: backward, bit 2: tail_rows_scatter)
+static int ln_form() {
+  static const int form = [] {
+    const char* e = getenv("PDAE_LN");
+    if (!e || !e[0] || e[0] == '1') return 7;
+    if (e[0] == '0') return 0;
+    return (strchr(e, 'f') ? 1 : 0) | (strchr(e, 'b') ? 2 : 0) | (strchr(e, 't') ? 4 : 0);
+  }();
+  return form;
+}
+
+template <int NS, int SLABS, typename... Args>
+static void ln_fwd_launch2(bool has_bias, bool has_pos, int M, hipStream_t s, Args... args) {
+  const dim3 grid((M + 3) / 4), block(256);
+  if (SLABS != 0 && has_bias) {
+    if (has_pos) hipLaunchKernelGGL((add_layernorm_fwd_kernel<NS, SLABS, SLABS != 0, true>), grid, block, 0, s, M, args...);
+    else hipLaunchKernelGGL((add_layernorm_fwd_kernel<NS, SLABS, SLABS != 0, false>), grid, block, 0, s, M, args...);
+  } else {
+    if (has_pos) hipLaunchKernelGGL((add_layernorm_fwd_kernel<NS, SLABS, false, true>), grid, block, 0, s, M, args...);
+    else hipLaunchKernelGGL((add_layernorm_fwd_kernel<NS, SLABS, false, false>), grid, block, 0, s, M, args...);
+  }
+}
+
+template <int NS>
+static void ln_fwd_launch(int slabs, int M, int C, const float* x, const float* pos, const float* gamma,
+                          const float* beta, float eps, float* xsum, float* y, float* mean, float* rstd,
+                          const float* br, const float* bias, const float* keep, int T, int br_slabs, hipStream_t s) {
+#define PDAE_LN_FWD(SL)                                                                                             \
+  ln_fwd_launch2<NS, SL>(bias != nullptr, pos != nullptr, M, s, C, x, pos, gamma, beta, eps, xsum, y, mean, rstd, \
+                         br, bias, keep, T, br_slabs)
+  switch (slabs) {
+    case 0: PDAE_LN_FWD(0); break;
+    case 1: PDAE_LN_FWD(1); break;
+    case 2: PDAE_LN_FWD(2); break;
+    case 3: if constexpr (NS == 2) { PDAE_LN_FWD(3); break; }
+    case 4: if constexpr (NS == 2) { PDAE_LN_FWD(4); break; }
+    default: PDAE_LN_FWD(-1); break;
+  }
+#undef PDAE_LN_FWD
+}
+
+template <int NS, int NW, int RPW>
+static void ln_bwd_launch(int slabs, int blocks, size_t lds, hipStream_t s, int M, int C, int rows, const float* dy,
+                          const float* x, const float* mean, const float* rstd, const float* gamma,
+                          const float* dres, float* dx, float* dgamma, float* dbeta, const float* keep, int T,
+                          float* da, float* dbias, int dy_slabs, float* dacc, int dacc_mode, float* part) {
+#define PDAE_LN_BWD2(SL, DR)                                                                                        \
+  hipLaunchKernelGGL((layernorm_bwd_kernel<NS, NW, SL, RPW, DR>), dim3(blocks), dim3(NW * 64), lds, s, M, C, rows, dy, \
+                     x, mean, rstd, gamma, dres, dx, dgamma, dbeta, keep, T, da, dbias, dy_slabs, dacc, dacc_mode, part)
+#define PDAE_LN_BWD(SL)         \
+  do {                          \
+    if (dres) PDAE_LN_BWD2(SL, true);  \
+    else PDAE_LN_BWD2(SL, false);      \
+  } while (0)
+  switch (slabs) {
+    case 1: PDAE_LN_BWD(1); break;
+    case 2: PDAE_LN_BWD(2); break;
+    case 3: if constexpr (NS == 2) { PDAE_LN_BWD(3); break; }
+    case 4: if constexpr (NS == 2 && RPW == 1) { PDAE_LN_BWD(4); break; }
+    default: PDAE_LN_BWD(-1); break;
+  }
+#undef PDAE_LN_BWD
+#undef PDAE_LN_BWD2
+}
+
 static int ln_forward(const char* what, int M, int C, int T, const float* x, const float* br,
                       const float* bias, const float* keep, const float* pos, const float* gamma,
                       const float* beta, float eps, float* xsum, float* y, float* mean, float* rstd,
@@ -410,8 +725,19 @@ static int ln_forward(const char* what, int M, int C, int T, const float* x, con
   if (M == 0) return PDAE_OK;
   if (!x || !gamma || !beta || !y || !mean || !rstd || ((pos || br) && !xsum) || ((bias || keep) && !br))
     return bad_arg("layernorm forward: null pointer");
-  hipLaunchKernelGGL(add_layernorm_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), M,
-                     C, x, pos, gamma, beta, eps, xsum, y, mean, rstd, br, bias, keep, T, br_slabs);
+  if (!(ln_form() & 1)) {
+    hipLaunchKernelGGL(add_layernorm_fwd_legacy_kernel, dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), M,
+                       C, x, pos, gamma, beta, eps, xsum, y, mean, rstd, br, bias, keep, T, br_slabs);
+    return check_launch(what);
+  }
+  // (8 slots: more than two slabs held at once would leave one wave per SIMD; they take the slab loop)
+  const int slabs = !br ? 0 : (br_slabs <= (C <= 512 ? 4 : 2) ? br_slabs : -1);
+  if (C <= 512)
+    ln_fwd_launch<2>(slabs, M, C, x, pos, gamma, beta, eps, xsum, y, mean, rstd, br, bias, keep, T, br_slabs,
+                     as_stream(stream));
+  else
+    ln_fwd_launch<LN_MAX4>(slabs, M, C, x, pos, gamma, beta, eps, xsum, y, mean, rstd, br, bias, keep, T, br_slabs,
+                           as_stream(stream));
   return check_launch(what);
 }
 
@@ -468,14 +794,28 @@ static int ln_backward(const char* what, int M, int C, int T, const float* dy, i
   // (the parameter gradients are then complete only after it): no atomics, no reduction launch per LayerNorm
   bool parked = false;
   if (!part && (part = deferred_take(blocks, nred * C, dgamma, C, dbeta, C, dbias, dbias ? C : 0))) parked = true;
-  if (C <= 512)
-    hipLaunchKernelGGL((layernorm_bwd_kernel<2, 16>), dim3(blocks), dim3(1024), 16 * nred * C * sizeof(float), s, M,
-                       C, rows, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, keep, T, da, dbias, dy_slabs,
-                       dacc, dacc_mode, part);
-  else
-    hipLaunchKernelGGL((layernorm_bwd_kernel<LN_MAX4, 4>), dim3(blocks), dim3(256), 4 * nred * C * sizeof(float), s,
-                       M, C, rows, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, keep, T, da, dbias, dy_slabs,
-                       dacc, dacc_mode, part);
+  // (compile-time slab counts as far as the rows in flight fit the registers: 128 per lane at 16 waves, two rows of four
+  //  slabs do not; 512 at 4 waves and 8 slots, three slabs do not.  The others take the slab loop.)
+  const int slabs = dy_slabs <= (C > 512 ? 2 : (rows == 16 ? 4 : 3)) ? dy_slabs : -1;
+  if (!(ln_form() & 2)) {
+    if (C <= 512)
+      hipLaunchKernelGGL((layernorm_bwd_legacy_kernel<2, 16>), dim3(blocks), dim3(1024), 16 * nred * C * sizeof(float),
+                         s, M, C, rows, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, keep, T, da, dbias,
+                         dy_slabs, dacc, dacc_mode, part);
+    else
+      hipLaunchKernelGGL((layernorm_bwd_legacy_kernel<LN_MAX4, 4>), dim3(blocks), dim3(256),
+                         4 * nred * C * sizeof(float), s, M, C, rows, dy, x, mean, rstd, gamma, dres, dx, dgamma,
+                         dbeta, keep, T, da, dbias, dy_slabs, dacc, dacc_mode, part);
+  } else if (C <= 512 && rows == 16) {
+    ln_bwd_launch<2, 16, 1>(slabs, blocks, 16 * nred * C * sizeof(float), s, M, C, rows, dy, x, mean, rstd, gamma,
+                            dres, dx, dgamma, dbeta, keep, T, da, dbias, dy_slabs, dacc, dacc_mode, part);
+  } else if (C <= 512) {
+    ln_bwd_launch<2, 16, 2>(slabs, blocks, 16 * nred * C * sizeof(float), s, M, C, rows, dy, x, mean, rstd, gamma,
+                            dres, dx, dgamma, dbeta, keep, T, da, dbias, dy_slabs, dacc, dacc_mode, part);
+  } else {
+    ln_bwd_launch<LN_MAX4, 4, 0>(slabs, blocks, 4 * nred * C * sizeof(float), s, M, C, rows, dy, x, mean, rstd, gamma,
+                                 dres, dx, dgamma, dbeta, keep, T, da, dbias, dy_slabs, dacc, dacc_mode, part);
+  }
   if (part && !parked) return det_reduce(s, blocks, nred * C, part, dgamma, C, dbeta, C, dbias, dbias ? C : 0);
   return check_launch(what);
 }
@@ -663,7 +1003,7 @@ __global__ __launch_bounds__(256) void tail_rows_gather_kernel(long long n4, int
   a_t[i] = a[src];
   if (b) b_t[i] = b[src];
 }
-__global__ __launch_bounds__(256) void tail_rows_scatter_kernel(long long n4, int C4, int T, int tail, const float4* __restrict__ da_t,
+__global__ __launch_bounds__(256) void tail_rows_scatter_legacy_kernel(long long n4, int C4, int T, int tail, const float4* __restrict__ da_t,
                                                                 const float4* __restrict__ db_t, float4* __restrict__ da,
                                                                 float4* __restrict__ db) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;   // over the FULL rows
@@ -676,6 +1016,25 @@ __global__ __launch_bounds__(256) void tail_rows_scatter_kernel(long long n4, in
   const long long src = (smp * tail + t) * C4 + c;
   da[i] = t >= 0 ? da_t[src] : zero;
   if (db) db[i] = t >= 0 ? db_t[src] : zero;
+}
+// (the form above selects between an address and a stack slot: flat loads; this one loads behind a guard)
+__global__ __launch_bounds__(256) void tail_rows_scatter_kernel(long long n4, int C4, int T, int tail, const float4* __restrict__ da_t,
+                                                                const float4* __restrict__ db_t, float4* __restrict__ da,
+                                                                float4* __restrict__ db) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;   // over the FULL rows
+  if (i >= n4) return;
+  const long long row = i / C4;
+  const int c = (int)(i - row * C4);
+  const long long smp = row / T;
+  const int t = (int)(row - smp * T) - (T - tail);
+  const long long src = (smp * tail + t) * C4 + c;
+  float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
+  if (t >= 0) {
+    va = da_t[src];
+    if (db) vb = db_t[src];
+  }
+  da[i] = va;
+  if (db) db[i] = vb;
 }
 
 // Y = epi(sum_s slabs[s] + bias): the consumer of split-K slabs where no LayerNorm follows (the coarse heads' Linear
@@ -730,9 +1089,9 @@ extern "C" int pdae_tail_rows_scatter(int B, int T, int tail, int C, const float
   if (B == 0) return PDAE_OK;
   if (!da_t || !da || (db && !db_t)) return bad_arg("tail_rows_scatter: null pointer");
   const long long n4 = (long long)B * T * (C / 4);
-  hipLaunchKernelGGL(tail_rows_scatter_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, as_stream(stream), n4, C / 4, T, tail,
-                     reinterpret_cast<const float4*>(da_t), reinterpret_cast<const float4*>(db_t), reinterpret_cast<float4*>(da),
-                     reinterpret_cast<float4*>(db));
+  hipLaunchKernelGGL((ln_form() & 4) ? tail_rows_scatter_kernel : tail_rows_scatter_legacy_kernel, dim3((unsigned)((n4 + 255) / 256)),
+                     dim3(256), 0, as_stream(stream), n4, C / 4, T, tail, reinterpret_cast<const float4*>(da_t),
+                     reinterpret_cast<const float4*>(db_t), reinterpret_cast<float4*>(da), reinterpret_cast<float4*>(db));
   return check_launch("tail_rows_scatter");
 }
 
