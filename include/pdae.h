@@ -1069,6 +1069,53 @@ int pdae_svm_ovo_predict(int m, int n, int ld, int K, int nC, const float* Gte, 
                          pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Pretraining validation's classifier (csrc/linsvc.hip; tools/runner_pretrain.py:25-48 of the reference fits
+ * sklearn.svm.LinearSVC(), i.e. liblinear's one-vs-rest L2-regularised squared-hinge machines with a regularised
+ * intercept): a truncated-Newton solver of all columns at once, in the primal.  Column k is the machine of class
+ * col0 + k: y_i = +1 where labels[i] == col0 + k, else -1;  f_k(w) = 1/2 |w|^2 + C sum_i max(0, 1 - y_i a_i.w)^2 with
+ * a_i = [x_i, 1].  The matrices are row-major fp32 with leading dimension ld (ncol <= ld <= 64): W, G, S, R, P, T over the
+ * D1 = D + 1 unknowns (row D the intercept), Z, AP, AS, V over the samples; the products Z = A W, AP = A P, AS = A S and
+ * T = A^T V are the caller's (pdae_rows_gemm).  sc: PDAE_LINSVC_SC doubles per column = f, |g|, |g(0)|, eps, r^T r,
+ * g^T s, the step taken, the line search's first step (the caller sets eps and the first step 1, zeros elsewhere);
+ * fl: PDAE_LINSVC_FL ints per column = done, Newton steps, CG active, capped, stalled, Hessian products, CG steps of this
+ * Newton step, failed line-search passes (zeros at the start).  A done column is skipped by every entry.  All sums have a
+ * fixed order and there are no atomics: two runs give the same bits.
+ *   linsvc_supported     host side, nothing launched: K < 2 classes, K > PDAE_LINSVC_MAX_CLASSES, empty input or a feature
+ *                        matrix beyond the row GEMMs' reach: PDAE_ERR_UNSUPPORTED.
+ *   linsvc_ones          A[r][col] = 1 for r < n: the intercept's column, set in the padding of the feature matrix.
+ *   linsvc_residual      over `rows` >= n rows.  mode 0: V = y o r o act with r = 1 - y o Z, act = r > 0 (the gradient is
+ *                        W - 2 C A^T V) and part[b][k] = the sum of r^2 over the active rows of row block b (64 rows; fp64);
+ *                        mode 1: V = act o AP for the columns whose CG is active (a Hessian product is P + 2 C A^T V).
+ *                        Rows >= n, columns >= ncol and skipped columns of V are written as zeros.
+ *   linsvc_newton_begin  per column, from T = A^T V and the nb row blocks' part: f, G = W - 2 C T, |g|; done when
+ *                        |g| <= eps |g(0)| (liblinear's rule: W starts at 0, so the first call's |g| is |g(0)|), capped
+ *                        and done when max_newton steps were taken; else S = 0, R = P = -G, CG active.
+ *   linsvc_cg_update     per column with CG active, from T = A^T (act o A P): alpha = r^T r / p^T H p, S += alpha P,
+ *                        R -= alpha H P; CG ends when |r| <= xi |g| or after cg_max steps, else P = R + beta P.
+ *   linsvc_linesearch    part[b][k][j] = the sum over row block b of max(0, 1 - y (Z + t AS))^2 at t = t0 2^-j, j = 0 .. 7.
+ *   linsvc_step          per column: the first t of that sequence with f(w + t s) - f(w) <= eta t g^T s is taken,
+ *                        W += t S; if none passes the next pass starts at t0 2^-8, and after four such passes (or when
+ *                        g^T s >= 0) the column is stalled and done.  Counts a Newton step either way.
+ *   linsvc_predict       pred[r] (int32) = the first column with the largest Z[r][k]; ncol == 1: Z[r][0] > 0 ? 1 : 0.     */
+#define PDAE_LINSVC_MAX_CLASSES 64
+#define PDAE_LINSVC_SC 8
+#define PDAE_LINSVC_FL 8
+int pdae_linsvc_supported(int n, int m, int D, int K);
+int pdae_linsvc_ones(int n, int ld, int col, float* A, pdae_stream_t stream);
+int pdae_linsvc_residual(int mode, int n, int rows, int ld, int ncol, int col0, const float* Z, const float* AP /*mode 1*/,
+                         const int* labels, const int* fl, float* V, double* part /*mode 0*/, pdae_stream_t stream);
+int pdae_linsvc_newton_begin(int D1, int ld, int ncol, int nb, double C, int max_newton, const float* W, const float* T,
+                             const double* part, float* G, float* S, float* R, float* P, double* sc, int* fl,
+                             pdae_stream_t stream);
+int pdae_linsvc_cg_update(int D1, int ld, int ncol, double C, double xi, int cg_max, const float* T, float* S, float* R,
+                          float* P, double* sc, int* fl, pdae_stream_t stream);
+int pdae_linsvc_linesearch(int n, int ld, int ncol, int col0, const float* Z, const float* AS, const int* labels,
+                           const double* sc, const int* fl, double* part, pdae_stream_t stream);
+int pdae_linsvc_step(int D1, int ld, int ncol, int nb, double C, double eta, float* W, const float* S, const float* G,
+                     const double* part, double* sc, int* fl, pdae_stream_t stream);
+int pdae_linsvc_predict(int m, int ld, int ncol, const float* Z, int* pred, pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Task-affinity protocol (csrc/affinity.hip; tools/runner_finetune.py:1198-1269 of the reference trains
  * nn.Linear(feat_dim, num_class) on the frozen encoder's features and reports the test cross-entropy and accuracy).
  *   linear_probe_train  trains W (K, D) and b (K) fp32 IN PLACE from their initial values on X (n x ld fp32, ld >= D)

@@ -144,6 +144,13 @@ _SIGNATURES = {
     "pdae_adamw_step_segments": [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp],
     "pdae_svm_ovo_train": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp],
     "pdae_svm_ovo_predict": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_linsvc_ones": [_i, _i, _i, _vp, _vp],
+    "pdae_linsvc_residual": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_linsvc_newton_begin": [_i, _i, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_linsvc_cg_update": [_i, _i, _i, ctypes.c_double, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_linsvc_linesearch": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_linsvc_step": [_i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdae_linsvc_predict": [_i, _i, _i, _vp, _vp, _vp],
     "pdae_linear_probe_train": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, _vp, _vp],
     "pdae_linear_probe_eval": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -179,6 +186,7 @@ _HOST = {
     "pdae_rows_gemm_bnrelu_stats_workspace": [_i, _i],
     "pdae_grad_norm_parts": [ctypes.c_longlong],
     "pdae_svm_ovo_supported": [_i, _i, _i, _vp, _vp, _i],
+    "pdae_linsvc_supported": [_i, _i, _i, _i],
     "pdae_linear_probe_supported": [_i, _i, _i, _i],
     "pdae_linear_probe_workspace": [_i, _i],
 }

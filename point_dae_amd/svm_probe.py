@@ -5,8 +5,9 @@ labelled cloud of the `extra_train` and `val` loaders is FPS-resampled to `npoin
 `return_feat` path gives one feature per cloud (max + mean pooled tokens for the Transformer variant,
 models/PointCAE_transformer.py:1024-1026; the global max-pooled feature for DGCNN / PointNet++), the
 features of all ranks are gathered, a sklearn LinearSVC is fitted on the train features and scored on
-the test features.  FPS and the encoders run on the gfx950 kernels; the SVM fit stays on the host as
-in the reference.
+the test features.  FPS and the encoders run on the gfx950 kernels.  The SVM fit is the reference's own call on the host
+(evaluate_svm; PDAE_LINSVC=sklearn, the default) or, with PDAE_LINSVC=hip, the batched Newton solver of linsvc_ops on the
+features as they lie on the device.
 """
 import numpy as np
 import torch
@@ -78,7 +79,11 @@ def validate(base_model, extra_train_loader, test_loader, epoch, config, log=pri
     tr_f, tr_l = extract_features(base_model, extra_train_loader, npoints)
     te_f, te_l = extract_features(base_model, test_loader, npoints)
     tr_f, tr_l, te_f, te_l = (_gather(t, world) for t in (tr_f, tr_l, te_f, te_l))
-    acc = evaluate_svm(tr_f.cpu().numpy(), tr_l.cpu().numpy(), te_f.cpu().numpy(), te_l.cpu().numpy())
+    from . import linsvc_ops
+    if linsvc_ops.backend() == 'hip' and tr_f.is_cuda:
+        acc = linsvc_ops.accuracy(tr_f, tr_l, te_f, te_l)
+    else:
+        acc = evaluate_svm(tr_f.cpu().numpy(), tr_l.cpu().numpy(), te_f.cpu().numpy(), te_l.cpu().numpy())
     if rank == 0:
         log('[Validation] EPOCH: %d  acc = %.4f' % (epoch, acc))
     base_model.train(was_training)

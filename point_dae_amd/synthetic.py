@@ -64,3 +64,22 @@ def labelled_clouds(count, N, seed=0, classes=3):
         p = p - p.mean(0, keepdims=True)
         out[b] = (p / np.sqrt((p ** 2).sum(1)).max()).astype(np.float32)
     return out, labels.astype(np.int64)
+
+
+def class_features(n, m, D, K, sep=1.0, seed=0, sizes=None):
+    """Labelled stand-in of pooled encoder features for the linear-SVM fits: class means (sep * unit normal) plus unit
+    noise, then a per-column scale (0.5 .. 2, log-uniform) and a constant offset of 3 -- the offset makes the intercept
+    matter and the scales give the columns uneven weight, like pooled tokens.  sizes: the classes' shares of the samples
+    (default: even).  Every class has at least two training samples.
+    -> (train (n, D) f32, train_labels (n,) i64, test (m, D) f32, test_labels (m,) i64)."""
+    rng = np.random.default_rng(seed)
+    means = sep * rng.standard_normal((K, D))
+    scale = np.exp(rng.uniform(np.log(0.5), np.log(2.0), D))
+    p = np.full(K, 1.0 / K) if sizes is None else np.asarray(sizes, np.float64) / np.sum(sizes)
+    ytr = np.concatenate([np.repeat(np.arange(K), 2), rng.choice(K, n - 2 * K, p=p)])
+    ytr = ytr[rng.permutation(n)]
+    yte = rng.choice(K, m, p=p)
+
+    def draw(y):
+        return ((means[y] + rng.standard_normal((len(y), D))) * scale + 3.0).astype(np.float32)
+    return draw(ytr), ytr.astype(np.int64), draw(yte), yte.astype(np.int64)
