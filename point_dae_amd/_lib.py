@@ -3,209 +3,71 @@
 This is the only place the product talks to native code.  There is no CPU
 fallback: if the library is missing, or a tensor is not a contiguous float32
 (int32 / int64 where the ABI says so) tensor on a HIP device, the call raises.
+
+include/pdae.h is the only place a signature or a constant of the ABI is written: parse_header() reads the
+declarations and the integer constants out of its text, once at import, and lib() binds every entry from them.  A new
+entry point needs its declaration in the header and nothing here.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PDAE_LIB") or os.path.join(_HERE, "libpdae_hip.so")     # PDAE_LIB: another build of the library (A/B runs, tools/lab/ab.sh)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pdae.h")
 
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-_f = ctypes.c_float
-
-# name -> argtypes (restype is always int unless listed in _STR)
-_SIGNATURES = {
-    "pdae_furthest_point_sampling": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_gather_points": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_gather_points_grad": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_resample_affine": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_ball_query": [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
-    "pdae_group_points": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_group_points_grad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_dropout_local": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_flatten_group_index": [_i, _i, _i, _vp, _vp, _vp],
-    "pdae_pipeline_norm_affine": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_pipeline_add_global": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_pipeline_add_local": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_pipeline_density": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_pipeline_subset": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_mask_propagate": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_three_nn": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_three_interpolate": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_three_interpolate_grad": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_knn": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_patch_affine": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_chamfer_forward": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_chamfer_backward": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_chamfer_backward_mean": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_mean_sum2": [ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
-    "pdae_rows_gemm": [_i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
-    "pdae_rows_gemm_batched": [_i, _i, _i, _i, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp],
-    "pdae_rows_wgrad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_rows_wgrad_multi": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_rows_wgrad_listed": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_sa_group_rows": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_sa_group_rows_grad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_embed_conv_groupbias_stats": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_embed_bnrelu_conv_groupmax": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_embed_bnrelu_conv_store_groupmax": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_embed_bnrelu_conv_store_groupmax_sum": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_group_max_scatter": [_i, _i, _vp, _vp, _vp, _vp],
-    "pdae_group_scatter_add": [_i, _i, _vp, _vp, _vp, _vp],
-    "pdae_bnrelu_backward": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
-    "pdae_attention_forward": [_i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
-    "pdae_attention_backward": [_i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_add_layernorm_forward": [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp],
-    "pdae_layernorm_backward": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
-    "pdae_bias_gelu_forward": [_i, _i, _vp, _vp, _vp, _vp],
-    "pdae_bias_gelu_backward": [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
-    "pdae_gelu_forward": [ctypes.c_longlong, _vp, _vp, _vp],
-    "pdae_gelu_backward": [ctypes.c_longlong, _vp, _vp, _vp, _vp],
-    "pdae_scale_residual": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_colsum": [_i, _i, _vp, _vp, _i, _vp],
-    "pdae_drop_path_keep": [_i, _i, _vp, _vp, _vp, _vp],
-    "pdae_tail_rows_gather": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_tail_rows_scatter": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_pos_embed_fc1": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_slab_sum_epi": [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
-    "pdae_residual_layernorm_forward": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp],
-    "pdae_residual_layernorm_backward": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
-    "pdae_scale_colsum": [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
-    "pdae_embed_conv1_stats": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_embed_conv1_backward_weight": [_i, _i, _vp, _vp, _vp, _vp],
-    "pdae_embed_bnrelu_backward_conv1_weight": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_bn_finalize": [_i, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_adamw_step": [ctypes.c_longlong, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp],
-    "pdae_masked_group_sums": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_group_sum_listed": [_i, _i, _vp, _vp, _vp, _vp],
-    "pdae_group_gemm_scatter": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
-    "pdae_group_gemm_scatter_add": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
-    "pdae_conv_stats": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_bnrelu_group_max": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_group_max_scatter_n": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_pool_bn_backward": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_fold_input": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_fold_input_grad": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_fold_input_rows": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_fold_out_backward": [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_deferred_flush": [_vp],
-    "pdae_emd_approxmatch": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_emd_matchcost": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_emd_matchcost_grad": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_rows_sqnorm": [_i, _i, _vp, _vp, _vp],
-    "pdae_gram_topk": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_xyz_topk": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_knn_reverse": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_edge_gather_stats": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_bn_lrelu_rows": [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
-    "pdae_bn_lrelu_backward_reduce": [ctypes.c_longlong, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_edge_backward": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_cloud_pool_stats": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_rows_pad": [ctypes.c_longlong, _i, _i, _vp, _vp, _vp],
-    "pdae_edge_weight_stack": [_i, _i, _i, _vp, _vp, _vp],
-    "pdae_edge_weight_stack_multi": [_i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_edge_weight_unstack_multi": [_i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_edge_weight_unstack": [_i, _i, _i, _vp, _vp, _vp],
-    "pdae_cloud_pool_backward": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_rows_gemm_bnrelu_stats": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_bnrelu_backward_apply": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
-    "pdae_bnrelu_backward_listed_apply": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp],
-    "pdae_max_plus_mean": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_max_plus_mean_grad": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_hcat": [_i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_pad2d": [_i, _i, _i, _i, _i, _vp, _vp, _vp],
-    "pdae_partials_sum_t": [_i, _i, _i, _vp, _vp, _vp],
-    "pdae_multi_copy": [_i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_assemble_tokens": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_assemble_tokens_grad": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_embed_split_conv3_weight": [_i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_embed_masked_prep": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_embed_masked_prep_fsum": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_embed_dw3_assemble": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_adamw_step_gscale": [ctypes.c_longlong, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp, _vp],
-    "pdae_prepend_token": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_prepend_token_grad": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_cls_max_concat": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_cls_max_concat_grad": [_i, _i, _i, _vp, _vp, _vp, _vp],
-    "pdae_bn_relu_dropout": [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp],
-    "pdae_bn_relu_dropout_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_softmax_xent": [_i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_softmax_xent_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_grad_norm_clip": [ctypes.c_longlong, _vp, _f, _vp, _vp, _vp, _vp],
-    "pdae_bn_lrelu_dropout": [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp],
-    "pdae_bn_lrelu_dropout_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_softmax_xent_smooth": [_i, _i, _f, _vp, _vp, _vp, _vp, _vp],
-    "pdae_softmax_xent_smooth_grad": [_i, _i, _f, _vp, _vp, _vp, _vp, _vp],
-    "pdae_bn_relu_dropout_eval_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_bn_lrelu_dropout_eval_grad": [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_adamw_step_segments": [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp],
-    "pdae_svm_ovo_train": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp],
-    "pdae_svm_ovo_predict": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_linsvc_ones": [_i, _i, _i, _vp, _vp],
-    "pdae_linsvc_residual": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_linsvc_newton_begin": [_i, _i, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_linsvc_cg_update": [_i, _i, _i, ctypes.c_double, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_linsvc_linesearch": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_linsvc_step": [_i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_linsvc_predict": [_i, _i, _i, _vp, _vp, _vp],
-    "pdae_linear_probe_train": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
-                                ctypes.c_double, ctypes.c_double, _vp, _vp],
-    "pdae_linear_probe_eval": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_vote_resample": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_vote_reduce": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_fewshot_batch": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_resident_batch": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_group_points_backward": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "pdae_rows_contract3": [_i, _i, _vp, _vp, _vp, _i, _vp, _vp],
-    "pdae_calib_mfma_bf16": [_i, _i, _vp, _vp, _vp, _vp],
-    "pdae_calib_copy": [ctypes.c_longlong, _vp, _vp, _vp],
-}
-# host-side queries (no stream argument)
-_HOST = {
-    "pdae_rows_gemm_plan": [_i, _i, _i, _i, _i, _vp, _vp, _vp],
-    "pdae_rows_wgrad_workspace": [_i, _i, _vp, _vp, _vp],
-    "pdae_rows_wgrad_multi_workspace": [_i, _vp, _vp, _vp, _vp],
-    "pdae_set_deterministic": [_vp, ctypes.c_size_t],
-    "pdae_deferred_begin": [_vp, ctypes.c_size_t],
-    "pdae_fold_input_grad_parts": [_i, _i],
-    "pdae_embed_conv1_backward_weight_parts": [_i],
-    "pdae_fold_out_backward_parts": [ctypes.c_longlong],
-    "pdae_pool_bn_backward_workspace": [ctypes.c_longlong, _i],
-    "pdae_deterministic": [],
-    "pdae_set_gemm_arith": [_i],
-    "pdae_gemm_arith": [],
-    "pdae_edge_parts": [],
-    "pdae_ctx_create": [_vp],
-    "pdae_ctx_destroy": [_vp],
-    "pdae_ctx_set_current": [_vp],
-    "pdae_ctx_current": [],
-    "pdae_cloud_pool_splits": [_i, _i],
-    "pdae_rows_gemm_bnrelu_stats_workspace": [_i, _i],
-    "pdae_grad_norm_parts": [ctypes.c_longlong],
-    "pdae_svm_ovo_supported": [_i, _i, _i, _vp, _vp, _i],
-    "pdae_linsvc_supported": [_i, _i, _i, _i],
-    "pdae_linear_probe_supported": [_i, _i, _i, _i],
-    "pdae_linear_probe_workspace": [_i, _i],
-}
-_STR = ("pdae_version", "pdae_last_error")
-
-_lib = None
+# the header's value types; every pointer and array parameter is a c_void_p.  Closed: anything else raises.
+_CTYPES = {'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'long long': ctypes.c_longlong, 'int64_t': ctypes.c_longlong,
+           'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t,
+           'pdae_stream_t': ctypes.c_void_p, 'pdae_ctx_t': ctypes.c_void_p}
 
 
 class NativeLibraryMissing(RuntimeError):
     pass
 
 
+def _ctype(decl, name, ret=False):
+    """ctypes type of one parameter (its name may be absent) or, with `ret`, of a return type."""
+    words = re.sub(r'\bconst\b', ' ', decl).split()
+    if '*' in decl or decl.rstrip().endswith(']'):
+        return ctypes.c_char_p if ret and ''.join(words) == 'char*' else ctypes.c_void_p
+    for n in (len(words), len(words) - (not ret)):      # all words are the type, or the last is a parameter's name
+        if ' '.join(words[:n]) in _CTYPES:
+            return _CTYPES[' '.join(words[:n])]
+    raise ValueError(f"{name}: type of '{decl.strip()}' is outside the ABI's type map")
+
+
+def parse_header(text):
+    """(decls, const) of a header's text: decls = {name: (restype, argtypes)} of every
+    `ret pdae_name(params);`, const = {PDAE_X: int} of the `#define PDAE_X <int>` lines and the enum items."""
+    text = re.sub(r'//[^\n]*', ' ', re.sub(r'/\*.*?\*/', ' ', text, flags=re.S))
+    const = {k: int(v) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(PDAE_\w+)[ \t]+(-?\d+)[ \t]*$', text, flags=re.M)}
+    text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)
+    const.update((k, int(v)) for k, v in re.findall(r'\b(PDAE_\w+)\s*=\s*(-?\d+)', text))
+    decls = {}
+    for ret, name, params in re.findall(r'([\w\s*]+?)\b(pdae_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', text):
+        params = [] if params.strip() in ('', 'void') else params.split(',')
+        decls[name] = (_ctype(ret, name, ret=True), [_ctype(p, name) for p in params])
+    return decls, const
+
+
+if not os.path.exists(HEADER_PATH):
+    raise NativeLibraryMissing(f"{HEADER_PATH} not found: the binding reads the C ABI from the tree's include/pdae.h")
+with open(HEADER_PATH) as _f:
+    _DECLS, CONST = parse_header(_f.read())
+
+_lib = None
+
+
 def exported_symbols():
     """Every symbol include/pdae.h declares (used by the CPU-side ABI test)."""
-    return list(_SIGNATURES) + list(_HOST) + list(_STR)
+    return list(_DECLS)
 
 
 def lib():
-    """Load libpdae_hip.so (built by __graft_entry__.build / csrc/Makefile)."""
+    """Load libpdae_hip.so (built by __graft_entry__.build / csrc/Makefile) and bind every entry include/pdae.h declares."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -213,17 +75,9 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (hipcc --offload-arch=gfx950). point_dae_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in _SIGNATURES.items():
+        for name, (restype, argtypes) in _DECLS.items():
             fn = getattr(handle, name)
-            fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
-        for name, argtypes in _HOST.items():
-            fn = getattr(handle, name)
-            fn.argtypes = argtypes
-            fn.restype = (ctypes.c_longlong if name.endswith('_workspace') and 'wgrad' not in name else
-                          ctypes.c_void_p if name == 'pdae_ctx_current' else ctypes.c_int)
-        for name in _STR:
-            getattr(handle, name).restype = ctypes.c_char_p
+            fn.argtypes, fn.restype = argtypes, restype
         _lib = handle
     return _lib
 
@@ -289,6 +143,15 @@ def stream_ptr():
 
 def ptr(t):
     return t.data_ptr() if t is not None else None
+
+
+def ptr_array(tensors):
+    """HOST array of the tensors' device pointers (None: NULL)."""
+    return (ctypes.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
+
+
+def int_array(values):
+    return (ctypes.c_int * len(values))(*values)
 
 
 def require(t, name, dtype=torch.float32, dim=None):
@@ -383,7 +246,7 @@ def rows_gemm_plan(M, N, K, w_kn, may_split):
 
 _wg_cache = {}
 
-GEMM_F32MFMA, GEMM_BF16X3 = 0, 1
+GEMM_F32MFMA, GEMM_BF16X3 = CONST['PDAE_GEMM_F32MFMA'], CONST['PDAE_GEMM_BF16X3']
 
 
 def gemm_arith():
@@ -405,29 +268,22 @@ def rows_wgrad_workspace(M, Ns, Ks):
     hit = _wg_cache.get(key)
     if hit is None:
         handle = lib()
-        n = len(Ns)
-        arr = ctypes.c_int * n
         floats = ctypes.c_longlong(0)
         _check(handle, 'pdae_rows_wgrad_workspace',
-               handle.pdae_rows_wgrad_workspace(M, n, arr(*Ns), arr(*Ks), ctypes.byref(floats)))
+               handle.pdae_rows_wgrad_workspace(M, len(Ns), int_array(Ns), int_array(Ks), ctypes.byref(floats)))
         hit = _wg_cache[key] = floats.value
     return hit
 
 
 def rows_wgrad(on, M, dYs, Xs, dWs, dbs, workspace):
     """pdae_rows_wgrad over lists of tensors (dbs entries may be None)."""
-    n = len(dYs)
-    parr, iarr = ctypes.c_void_p * n, ctypes.c_int * n
-    call('pdae_rows_wgrad', on, M, n, parr(*[ptr(t) for t in dYs]), parr(*[ptr(t) for t in Xs]),
-         parr(*[ptr(t) for t in dWs]), parr(*[ptr(t) for t in dbs]),
-         iarr(*[t.shape[1] for t in dYs]), iarr(*[t.shape[1] for t in Xs]), ptr(workspace))
+    call('pdae_rows_wgrad', on, M, len(dYs), ptr_array(dYs), ptr_array(Xs), ptr_array(dWs), ptr_array(dbs),
+         int_array([t.shape[1] for t in dYs]), int_array([t.shape[1] for t in Xs]), ptr(workspace))
 
 
 def edge_weights_multi(name, on, cos, cins, kps, srcs, dsts):
     """pdae_edge_weight_stack_multi / _unstack_multi over lists (HOST arrays of sizes and device pointers)."""
-    n = len(cos)
-    parr, iarr = ctypes.c_void_p * n, ctypes.c_int * n
-    call(name, on, n, iarr(*cos), iarr(*cins), iarr(*kps), parr(*[ptr(t) for t in srcs]), parr(*[ptr(t) for t in dsts]))
+    call(name, on, len(cos), int_array(cos), int_array(cins), int_array(kps), ptr_array(srcs), ptr_array(dsts))
 
 
 class AdamwSegment(ctypes.Structure):
@@ -436,7 +292,7 @@ class AdamwSegment(ctypes.Structure):
                 ('weight_decay', ctypes.c_float)]
 
 
-ADAMW_MAX_SEGMENTS = 8
+ADAMW_MAX_SEGMENTS = CONST['PDAE_ADAMW_MAX_SEGMENTS']
 
 
 def adamw_step_segments(flat_param, flat_grad, exp_avg, exp_avg_sq, segments, beta1, beta2, eps, step, gscale=None):
@@ -475,14 +331,13 @@ def multi_copy(pairs, strided=()):
     for d, s_, c in strided:
         if s_.dim() != 2 or not 0 < c <= s_.shape[1] or d.numel() != s_.shape[0] * c:
             raise ValueError('multi_copy: %r <- %r[:, :%d]' % (tuple(d.shape), tuple(s_.shape), c))
-    parr, larr, iarr = ctypes.c_void_p * n, ctypes.c_longlong * n, ctypes.c_int * n
-    src = parr(*([ptr(s_) for _, s_ in pairs] + [ptr(s_) for _, s_, _ in strided]))
-    dst = parr(*([ptr(d) for d, _ in pairs] + [ptr(d) for d, _, _ in strided]))
-    cnt = larr(*([d.numel() for d, _ in pairs] + [d.numel() for d, _, _ in strided]))
+    src = ptr_array([s_ for _, s_ in pairs] + [s_ for _, s_, _ in strided])
+    dst = ptr_array([d for d, _ in pairs] + [d for d, _, _ in strided])
+    cnt = (ctypes.c_longlong * n)(*([d.numel() for d, _ in pairs] + [d.numel() for d, _, _ in strided]))
     cols = sld = None
     if strided:
-        cols = iarr(*([0] * len(pairs) + [c for _, _, c in strided]))
-        sld = iarr(*([0] * len(pairs) + [s_.shape[1] for _, s_, _ in strided]))
+        cols = int_array([0] * len(pairs) + [c for _, _, c in strided])
+        sld = int_array([0] * len(pairs) + [s_.shape[1] for _, s_, _ in strided])
     call('pdae_multi_copy', on, n, src, dst, cnt, cols, sld)
 
 
@@ -492,9 +347,8 @@ def rows_wgrad_multi(jobs):
     for i in range(0, len(jobs), WGRAD_MULTI_MAX):
         part = jobs[i:i + WGRAD_MULTI_MAX]
         n = len(part)
-        parr, iarr = ctypes.c_void_p * n, ctypes.c_int * n
-        Ms, Ns, Ks = (iarr(*v) for v in ([j[0].shape[0] for j in part], [j[0].shape[1] for j in part],
-                                        [j[1].shape[1] for j in part]))
+        Ms, Ns, Ks = (int_array(v) for v in ([j[0].shape[0] for j in part], [j[0].shape[1] for j in part],
+                                             [j[1].shape[1] for j in part]))
         key = ('multi', tuple(Ms), tuple(Ns), tuple(Ks), lib().pdae_gemm_arith())
         floats = _wg_cache.get(key)
         if floats is None:
@@ -504,5 +358,4 @@ def rows_wgrad_multi(jobs):
             floats = _wg_cache[key] = f.value
         on = part[0][0]
         ws = torch.empty(max(floats, 1), device=on.device, dtype=torch.float32)
-        call('pdae_rows_wgrad_multi', on, n, Ms, parr(*[ptr(j[0]) for j in part]), parr(*[ptr(j[1]) for j in part]),
-             parr(*[ptr(j[2]) for j in part]), parr(*[ptr(j[3]) for j in part]), Ns, Ks, ptr(ws))
+        call('pdae_rows_wgrad_multi', on, n, Ms, *(ptr_array([j[c] for j in part]) for c in range(4)), Ns, Ks, ptr(ws))

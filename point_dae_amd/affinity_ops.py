@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 
-BATCH = 64                                           # include/pdae.h PDAE_PROBE_BATCH
+BATCH = _lib.CONST['PDAE_PROBE_BATCH']
 BETAS, EPS = (0.9, 0.999), 1e-8                       # torch.optim.AdamW's defaults, which the reference keeps
 
 

@@ -43,7 +43,7 @@ CG_ROUND = 8                       # conjugate-gradient steps between two reads 
 CG_XI = 0.01                       # conjugate gradients end at |r| <= CG_XI |g| (0.1 took three times the Newton steps)
 ARMIJO_ETA = 1e-2                  # liblinear's line-search constant
 ROW_BLOCK = 64                     # csrc/linsvc.hip LS_ROWS
-SC, FL = 8, 8                      # include/pdae.h PDAE_LINSVC_SC / _FL
+SC, FL = _lib.CONST['PDAE_LINSVC_SC'], _lib.CONST['PDAE_LINSVC_FL']
 SC_F, SC_GNORM, SC_GNORM0, SC_EPS, SC_RR, SC_GS, SC_T, SC_T0 = range(8)
 FL_DONE, FL_NEWTON, FL_CG_ACTIVE, FL_CAPPED, FL_STALLED, FL_HV, FL_CG_ITERS, FL_LS_FAILS = range(8)
 

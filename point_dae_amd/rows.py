@@ -11,7 +11,6 @@ sa_mlp.py all take these from here and from nowhere else:
     bn_finalize, bn_eval_affine);
   * linear_any: x W^T + b (+ ReLU) for any K, N as one autograd node.
 """
-import ctypes
 import os
 
 import torch
@@ -72,11 +71,9 @@ def pad2d(x, pr, pc):
 
 def _hcat(pieces, R, like):
     """pieces: [(2-D tensor or None, cols)] -> (R, sum cols) with the pieces' leading columns side by side (None: zeros)."""
-    k = len(pieces)
     out = empty((R, sum(c for _, c in pieces)), like)
-    parr, iarr = ctypes.c_void_p * k, ctypes.c_int * k
-    _lib.call('pdae_hcat', like, k, R, parr(*[_lib.ptr(t) for t, _ in pieces]), iarr(*[c for _, c in pieces]),
-              iarr(*[(t.stride(0) if t is not None else c) for t, c in pieces]), _lib.ptr(out))
+    _lib.call('pdae_hcat', like, len(pieces), R, _lib.ptr_array([t for t, _ in pieces]), _lib.int_array([c for _, c in pieces]),
+              _lib.int_array([(t.stride(0) if t is not None else c) for t, c in pieces]), _lib.ptr(out))
     return out
 
 
@@ -131,11 +128,9 @@ class _SplitWeightCols(torch.autograd.Function):
         gs = [g.contiguous() if g is not None else None for g in gs]
         like = next(g for g in gs if g is not None)
         srcs = [g if g is not None else torch.zeros((R, n + (-n) % 4), device=like.device) for g, n in zip(gs, widths)]
-        k = len(srcs)
         dw = empty((R, C), like)
-        parr, iarr = ctypes.c_void_p * k, ctypes.c_int * k
-        _lib.call('pdae_hcat', like, k, R, parr(*[_lib.ptr(t) for t in srcs]), iarr(*widths), iarr(*[t.shape[1] for t in srcs]),
-                  _lib.ptr(dw))
+        _lib.call('pdae_hcat', like, len(srcs), R, _lib.ptr_array(srcs), _lib.int_array(widths),
+                  _lib.int_array([t.shape[1] for t in srcs]), _lib.ptr(dw))
         return (dw,) + (None,) * len(ctx.bounds)
 
 

@@ -22,7 +22,7 @@ import torch
 from . import _lib
 from .rows import pad2d, rows_gemm
 
-MAX_PAIR = 2048                                       # include/pdae.h PDAE_SVM_MAX_PAIR
+MAX_PAIR = _lib.CONST['PDAE_SVM_MAX_PAIR']
 MAX_ITER = 1000000
 SVM_CS = tuple(10 ** i for i in range(-3, 3))         # runner_finetune.py:1039-1040
 

@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from .pointnet2_utils import gather_operation
 
-MAX_CLASSES = 64                                      # include/pdae.h PDAE_VOTE_MAX_CLASSES
+MAX_CLASSES = _lib.CONST['PDAE_VOTE_MAX_CLASSES']
 # the kernels index a forward's intermediates with 32-bit element counts (the library refuses 2^31 elements); the largest
 # either classifier makes per cloud is DGCNN's (N, N) Gram matrix, or its (N, 1024) conv5 rows
 MAX_FORWARD_ELEMENTS = 1 << 31
