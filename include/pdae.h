@@ -233,6 +233,44 @@ int pdae_mask_propagate(int parents, int k, int children, const uint8_t* parent_
                         uint8_t* child_masked, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Point-M2AE hierarchical encoder in evaluation mode, forward only (csrc/m2ae.hip; H_Encoder.forward with eval=True,
+ * models/Point_M2AE.py:99-180; Token_Embed, models/Point_M2AE_modules.py:169-216; Attention, :269-305).
+ * attention_local_forward: qkv (B*T, 3*H*D) rows [3][H][D], centres (B*T, 3) with the padded rows zero, len (B) i32
+ *   visible tokens per sample (len[b] <= T) -> o (B*T, H*D) = softmax(q k^T * scale + mask * -100000) v with
+ *   mask[b][q][k] = !(q < len[b] && k < len[b]) && (radius == 0 || |centre_q - centre_k| >= radius), evaluated in
+ *   the kernel; no (B, T, T) tensor is read or written.  Masked pairs are left out of the softmax, which is the
+ *   reference's -100000 in fp32 for every row that keeps a key.  With radius == 0 a padded query row (q >= len[b])
+ *   keeps none: its output, which nobody reads, is written as zeros.  D in {16, 32, 64}, 1 <= T <= 512, any T.
+ *   No log-sum-exp is kept: there is no backward.
+ * m2ae_compact: masked (B, G) u8 -> len (B) = visible tokens per sample, ids (B, G) i32 = their indices in ascending
+ *   order, -1 behind them.
+ * m2ae_pack: x (B*T_pad, C) / cen (B*T_pad, 3) = the visible tokens / centres of tokens (B*G, C) / centres (B*G, 3) at
+ *   the front of each sample, zeros behind them (T_pad >= max len).  m2ae_unpack: rows t < len[b] of x back to rows
+ *   ids[b][t] of tokens; other rows of tokens are not touched.  C % 4 == 0.
+ * m2ae_group_max: out (P, C) = max over the n consecutive rows of each patch of x (P*n, C).
+ * m2ae_gather_max: out (P, C) = max over the k rows idx[p][.] (i64, flat) of x.
+ * m2ae_gather_add_relu: out (P*k, C), row (p, j) = relu(x[idx[p][j]] + g[p]).
+ * m2ae_embed_tail: tok (R/n, N4) = max over each patch's n rows of relu(F (R, K) Wl (N3, K)^T + gb[patch] (R/n, N3))
+ *   W4 (N4, N3)^T, + b4: second_conv of Token_Embed(3 -> C) with the BatchNorm folded into Wl / gb; neither the
+ *   (R, N3) nor the (R, N4) product is stored.  n in {4, 8, 16, 32}, K % 8 == 0, K <= 256, N3 % 128 == 0,
+ *   N4 % 32 == 0, N4 <= 128.
+ */
+int pdae_attention_local_forward(int B, int T, int H, int D, float scale, float radius, const float* qkv,
+                                 const float* centres, const int32_t* len, float* o, pdae_stream_t stream);
+int pdae_m2ae_compact(int B, int G, const uint8_t* masked, int32_t* len, int32_t* ids, pdae_stream_t stream);
+int pdae_m2ae_pack(int B, int G, int Tp, int C, const int32_t* ids, const int32_t* len, const float* tokens,
+                   const float* centres, float* x, float* cen, pdae_stream_t stream);
+int pdae_m2ae_unpack(int B, int G, int Tp, int C, const int32_t* ids, const int32_t* len, const float* x,
+                     float* tokens, pdae_stream_t stream);
+int pdae_m2ae_group_max(long long P, int n, int C, const float* x, float* out, pdae_stream_t stream);
+int pdae_m2ae_gather_max(long long P, int k, int C, const float* x, const int64_t* idx, float* out,
+                         pdae_stream_t stream);
+int pdae_m2ae_gather_add_relu(long long P, int k, int C, const float* x, const int64_t* idx, const float* g,
+                              float* out, pdae_stream_t stream);
+int pdae_m2ae_embed_tail(long long R, int n, int K, int N3, int N4, const float* F, const float* Wl, const float* gb,
+                         const float* W4, const float* b4, float* tok, pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Loader-side corruption on the device.  Replaces corrupt_dropout_local
  *   datasets/corrupt_util.py:590-612, which the reference runs per item in its
  *   DataLoader workers (ShapeNet55Dataset.__getitem__ :90-119).
