@@ -553,6 +553,24 @@ long long pdae_pool_bn_backward_workspace(long long G, int C);
 int pdae_pool_bn_backward(long long G, int ns, int C, const float* grad, const unsigned char* arg,
                           const float* out, const float* y, const float* mean, const float* invstd,
                           const float* gamma, float* S, float* workspace, float* dy, pdae_stream_t stream);
+/* One set-abstraction level in EVALUATION mode, forward only, as one kernel (csrc/sa_eval.hip;
+ * extensions/pointnet2/pointnet2_modules.py:31-72,124-158 with every BatchNorm2d on its running estimates, i.e. the
+ * per-channel affine scale_l = gamma / sqrt(var + eps), shift_l = beta - mean * scale_l):
+ *   out[b*np + p, :] = max over s of relu(scale2 (W2 relu(scale1 (W1 relu(scale0 (P[b*N + j] + W0x d) + shift0)) + shift1))
+ *                      + shift2),   j = idx[b,p,s],  d = xyz[b,j] - new_xyz[b,p]
+ * xyz (B,N,3), new_xyz (B,np,3), idx (B,np,ns) i32; P (B*N, C1) = features (B*N, C0) . W0f^T, the feature columns of the
+ * first layer's weight applied once per SOURCE point by the caller (NULL exactly when C0 == 0); W0x (C1, 3) its
+ * coordinate columns, applied per (centre, sample) on the centred difference; W1 (C2, C1), W2 (C3, C2); out (B*np, C3).
+ * No (B np ns, .) tensor exists; no atomics, fixed reduction order.  An index outside [0, N) is clamped.
+ * sa_eval_supported: 1 when the kernel takes the layout -- ns 32 or 64 and (C1, C2, C3) = (64, 64, 128) or
+ * (128, 128, 256) -- else 0; sa_eval_forward returns PDAE_ERR_UNSUPPORTED for every other before anything is launched.
+ * P, scale0, shift0, W1, W2 16-byte aligned. */
+int pdae_sa_eval_supported(int ns, int C0, int C1, int C2, int C3);
+int pdae_sa_eval_forward(int B, int N, int np, int ns, int C0, int C1, int C2, int C3, const float* xyz,
+                         const float* new_xyz, const int32_t* idx, const float* P /*nullable, C0 = 0*/, const float* W0x,
+                         const float* scale0, const float* shift0, const float* W1, const float* scale1,
+                         const float* shift1, const float* W2, const float* scale2, const float* shift2, float* out,
+                         pdae_stream_t stream);
 
 /* First layer of the FoldingNet stage of Point_CAE_PointNetv2 (csrc/folding.hip;
  * models/PointCAE_pointnetv2.py:157-167: folding2[0] over [grid(2) | coarse point(3) |

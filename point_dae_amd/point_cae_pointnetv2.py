@@ -25,9 +25,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, nn_ops, sa_mlp
+from . import _lib, nn_ops, sa_eval_ops, sa_mlp
 from .arena import begin_step
 from .chamfer_dist import ChamferDistanceL1, ChamferDistanceL2
+from .classifier import Classifier
 from .corrupt_util_tensor import corrupt_in_forward
 from .pointnet2_utils import ball_query, furthest_point_sample_with_centres
 from .registry import MODELS
@@ -100,23 +101,34 @@ class _GroupRows(torch.autograd.Function):
 
 
 class PointnetSAModule(nn.Module):
-    """FPS -> ball query -> group (centre-subtracted xyz || features) -> shared MLP -> max."""
+    """FPS -> ball query -> group (centre-subtracted xyz || features) -> shared MLP -> max.
+    fused_eval: in evaluation mode take the forward-only level of sa_eval_ops (PDAE_SA_EVAL=hip, the default) where it
+    takes the layout; off (the default), and in training mode, forward is untouched by it."""
 
-    def __init__(self, mlp, npoint=None, radius=None, nsample=None, use_xyz=True):
+    def __init__(self, mlp, npoint=None, radius=None, nsample=None, use_xyz=True, fused_eval=False):
         super().__init__()
         self.npoint, self.radius, self.nsample = npoint, radius, nsample
+        self.fused_eval = bool(fused_eval) and use_xyz
         spec = list(mlp)
         if use_xyz:
             spec[0] += 3
         self.mlps = nn.ModuleList([SharedMLP(spec)])
 
-    def forward(self, xyz, features=None):
-        """xyz (B,N,3); features rows (B*N, C) or None -> new_xyz (B,np,3), rows (B*np, C')."""
+    def forward(self, xyz, features=None, capture=None):
+        """xyz (B,N,3); features rows (B*N, C) or None -> new_xyz (B,np,3), rows (B*np, C').  capture: a dict that
+        receives the level's FPS and ball-query indices (tests)."""
         B, N, _ = xyz.shape
+        fused = self.fused_eval and not self.training and sa_eval_ops.mode() == 'hip'
         if self.npoint is not None:
             with torch.no_grad():
-                _, new_xyz = furthest_point_sample_with_centres(xyz, self.npoint)
+                fps_idx, new_xyz = furthest_point_sample_with_centres(xyz, self.npoint)
                 idx = ball_query(self.radius, self.nsample, xyz, new_xyz)          # (B,np,ns) i32
+            if capture is not None:
+                capture.update(fps_idx=fps_idx, ball_idx=idx)
+            if fused:
+                out = sa_eval_ops.level(xyz, new_xyz, idx, features, list(self.mlps[0]))
+                if out is not None:              # (None: a layout the kernel refuses -- the layer-by-layer form below)
+                    return new_xyz, out
             C = 0 if features is None else features.shape[1]
             if (C % 4 == 0 and C <= 1024 and N <= 4096 and
                     4 * (2 * N + 1 + self.npoint * self.nsample) <= 150 * 1024):     # (a cloud's sort lives in LDS)
@@ -130,6 +142,10 @@ class PointnetSAModule(nn.Module):
             groups, per = B * self.npoint, self.nsample
         else:
             new_xyz = None
+            if fused:
+                out = sa_eval_ops.group_all(xyz, features, list(self.mlps[0]))
+                if out is not None:
+                    return new_xyz, out
             g = xyz.reshape(B * N, 3)
             g = torch.cat([g, g.new_zeros(g.shape[0], 1)] + ([features] if features is not None else []), dim=1)
             groups, per = B, N
@@ -143,16 +159,19 @@ class PointnetSAModule(nn.Module):
 
 
 class PointNetv2_encoder(nn.Module):
-    def __init__(self, num_channel=3):
+    def __init__(self, num_channel=3, fused_eval=False):
         super().__init__()
-        self.sa1 = PointnetSAModule(npoint=512, radius=0.2, nsample=32, mlp=[0, 64, 64, 128])
-        self.sa2 = PointnetSAModule(npoint=128, radius=0.4, nsample=64, mlp=[128, 128, 128, 256])
-        self.sa3 = PointnetSAModule(mlp=[256, 256, 512, 1024])
+        self.sa1 = PointnetSAModule(npoint=512, radius=0.2, nsample=32, mlp=[0, 64, 64, 128], fused_eval=fused_eval)
+        self.sa2 = PointnetSAModule(npoint=128, radius=0.4, nsample=64, mlp=[128, 128, 128, 256], fused_eval=fused_eval)
+        self.sa3 = PointnetSAModule(mlp=[256, 256, 512, 1024], fused_eval=fused_eval)
 
-    def forward(self, xyz):
-        l1_xyz, l1 = self.sa1(xyz, None)
-        l2_xyz, l2 = self.sa2(l1_xyz, l1)
+    def forward(self, xyz, capture=None):
+        caps = [None if capture is None else {} for _ in range(2)]
+        l1_xyz, l1 = self.sa1(xyz, None, caps[0])
+        l2_xyz, l2 = self.sa2(l1_xyz, l1, caps[1])
         _, l3 = self.sa3(l2_xyz, l2)
+        if capture is not None:
+            capture.update(fps_idx=[c['fps_idx'] for c in caps], ball_idx=[c['ball_idx'] for c in caps], levels=[l1, l2])
         return l3                                                  # (B, 1024)
 
 
@@ -214,3 +233,40 @@ class Point_CAE_PointNetv2(nn.Module):
         if capture is not None:
             capture.update(feature=feature, coarse=coarse, fine=fine)
         return self.loss_func(coarse, pts), self.loss_func(fine, pts)
+
+
+SMOOTH_EPS = 0.3           # get_loss_acc's label smoothing (PointCAE_pointnetv2.py:950-957)
+
+
+@MODELS.register_module()
+class PointNetv2_feat(Classifier):
+    """models/PointCAE_pointnetv2.py:936-1017: the PointNet++ encoder as the frozen feature extractor of
+    --svm_classification -- pointnetv2_encoder and nothing else that carries parameters, so a Point_CAE_PointNetv2
+    checkpoint loads with folding1.* / folding2.* unexpected and nothing missing.  get_loss_acc, load_model_from_ckpt and
+    _init_weights are the classifier's (the reference's class carries copies).  Forward only, evaluation mode only, no CPU
+    path: the encoder runs its levels on sa_eval_ops (PDAE_SA_EVAL=hip, the default; =layers: layer by layer)."""
+
+    def __init__(self, config, **kwargs):
+        super().__init__()
+        self.config = config
+        self.cls_dim = config.cls_dim
+        self.smoothing = bool(config.get('smoothloss', False))
+        self.pointnetv2_encoder = PointNetv2_encoder(fused_eval=True)
+
+    @property
+    def smooth_eps(self):
+        return SMOOTH_EPS if self.smoothing else None
+
+    @torch.no_grad()
+    def forward(self, pts, capture=None):
+        """pts (B, N, 3+) -> the encoder's feature (B, 1024)."""
+        if self.training:
+            raise NotImplementedError('PointNetv2_feat: evaluation mode only -- the forward-only encoder of the linear-SVM '
+                                      'protocol; PointNet++ fine-tuning is not built')
+        if not pts.is_cuda:
+            raise RuntimeError('PointNetv2_feat: points must be on the GPU (there is no CPU path)')
+        begin_step(pts.device)
+        f = self.pointnetv2_encoder(pts[:, :, :3].contiguous(), capture)
+        if capture is not None:
+            capture.update(feature=f)
+        return f

@@ -1,5 +1,6 @@
 """Classification fine-tuning models, MI355X host side (models/Point_MAE.py:578-706 PointTransformer and :846-966
-PointTransformerLinearClassification of the reference; the two differ in cls_head_finetune only).
+PointTransformerLinearClassification of the reference; the two differ in cls_head_finetune only; :970-1092
+PointTransformerNoClassTokenSVMFeature, the frozen feature extractor of --svm_classification).
 
 Same parameter names and shapes as the reference, so a pretraining checkpoint of this repository loads through
 builder.remap_pretrain_keys (the 'MAE_encoder.' prefix dropped) with strict=False, reporting the same missing and
@@ -20,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import finetune_ops, nn_ops
+from .arena import begin_step
 from .classifier import Classifier
 from .point_cae_transformer import Encoder, Group, TransformerEncoder, pos_embed_layers, trunc_normal_
 from .registry import MODELS
@@ -105,3 +107,59 @@ class PointTransformerLinearClassification(_TransformerClassifier):
 
     def build_head(self):
         return nn.Sequential(nn.Linear(self.trans_dim * 2, self.cls_dim))
+
+
+@MODELS.register_module()
+class PointTransformerNoClassTokenSVMFeature(Classifier):
+    """Point_MAE.py:970-1092: the trunk without cls_token / cls_pos and without a head, T = num_group tokens per cloud;
+    the feature is max + mean over the normed tokens (:1092), what --svm_classification fits its SVMs on.  A Transformer
+    pretraining checkpoint loads with its decoder keys unexpected and nothing missing.  get_loss_acc, load_model_from_ckpt
+    and _init_weights are the classifier's (the reference's class carries copies).  Never trained: forward only,
+    evaluation mode only, no CPU path."""
+    late_grad_prefixes = ()
+
+    def __init__(self, config, **kwargs):
+        super().__init__()
+        self.config = config
+        self.trans_dim = config.trans_dim
+        self.depth = config.depth
+        self.drop_path_rate = config.drop_path_rate
+        self.cls_dim = config.cls_dim
+        self.num_heads = config.num_heads
+        self.group_size = config.group_size
+        self.num_group = config.num_group
+        self.encoder_dims = config.encoder_dims
+        if self.num_group > MAX_TOKENS:
+            raise NotImplementedError('PointTransformerNoClassTokenSVMFeature: num_group = %d tokens per cloud; the '
+                                      'attention kernels take at most %d' % (self.num_group, MAX_TOKENS))
+        if self.encoder_dims != self.trans_dim:
+            raise NotImplementedError('PointTransformerNoClassTokenSVMFeature: encoder_dims must equal trans_dim (the '
+                                      'tokens feed the blocks)')
+        self.group_divider = Group(num_group=self.num_group, group_size=self.group_size)
+        self.encoder = Encoder(encoder_channel=self.encoder_dims)
+        self.pos_embed = pos_embed_layers(self.trans_dim)
+        dpr = [x.item() for x in torch.linspace(0, self.drop_path_rate, self.depth)]
+        self.blocks = TransformerEncoder(self.trans_dim, self.depth, self.num_heads, dpr)
+        self.norm = nn.LayerNorm(self.trans_dim)
+
+    @torch.no_grad()
+    def forward(self, pts, capture=None):
+        """pts (B, N, 3+) -> the feature (B, trans_dim)."""
+        if self.training:
+            raise NotImplementedError('PointTransformerNoClassTokenSVMFeature: evaluation mode only -- the frozen feature '
+                                      'extractor of the linear-SVM protocol; PointTransformerNoClassToken fine-tuning is '
+                                      'not built')
+        if not pts.is_cuda:
+            raise RuntimeError('PointTransformerNoClassTokenSVMFeature: points must be on the GPU (there is no CPU path)')
+        pts = pts[:, :, :3].contiguous()
+        begin_step(pts.device)
+        B, G, C = pts.shape[0], self.num_group, self.trans_dim
+        neighborhood, center = self.group_divider(pts, capture)      # (capture also receives fps_idx, knn_idx)
+        tokens = self.encoder(neighborhood)                                           # (B, G, C)
+        pos = nn_ops.pos_embed(center.reshape(B * G, 3), self.pos_embed)
+        x = self.blocks(tokens.reshape(B * G, C), pos, B, G)         # nn_ops.Pending: the final norm adds the last branch
+        x = nn_ops.layer_norm(x, self.norm).reshape(B, G, C)
+        f = nn_ops.max_plus_mean(x)
+        if capture is not None:
+            capture.update(center=center, tokens=tokens, x=x, feature=f)
+        return f
