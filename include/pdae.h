@@ -1298,6 +1298,39 @@ int pdae_rows_contract3(int m, int c, const float* d, const float* w, const int6
                         float* dx, pdae_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The part-segmentation head in evaluation mode, forward only (csrc/partseg.hip; segmentation/models/pt.py:301-333 on
+ * PointNetFeaturePropagation, segmentation/models/pointnet2_utils.py:262-312, and the metric of segmentation/main.py:246-295
+ * of the reference; every BatchNorm as its running-estimate affine scale, shift).
+ *   partseg_supported        1 when 3 <= G <= 256 centres per cloud, the propagated width C is a positive multiple of 4, the
+ *                            tail's input width K is 256 and P is 50 part labels -- else 0; partseg_propagate / partseg_tail
+ *                            return PDAE_ERR_UNSUPPORTED for every other layout before anything is read or launched.
+ *   partseg_token_pool       F (B, G, C) -> out (B, 2C) = [max over G | mean over G] (the sum in token order, / G).
+ *   partseg_propagate        pts (B, N, 3), centres (B, G, 3), T (B*G, C) = the first layer's feature columns applied once per
+ *                            token (bias included), W0x (C, 3) its coordinate columns -> a0 (B*N, C) =
+ *                            relu(scale0 (sum_k w_k T[b, idx_k] + W0x p) + shift0): idx_k the three nearest centres by
+ *                            ((dx dx + dy dy) + dz dz), ties to the lower index; w_k = r_k / ((r_0 + r_1) + r_2),
+ *                            r_k = 1 / (d_k + 1e-8).  idx3 (B, N, 3) int32 receives the indices, nearest first (nullable).
+ *                            T, scale0, shift0, a0 16-byte aligned.
+ *   partseg_cloud_bias_relu  y (B*N, C) <- relu(y + gbias[b]) in place, gbias (B, C); C a multiple of 4.
+ *   partseg_tail             y (S*N, 256) -> logp (S*N, 50) fp32 = log_softmax(relu(y scale + shift) W3^T + b3) as
+ *                            (x - max) - log sum exp(x - max); pred (S*N) int32 = the argmax of the stored logp over
+ *                            [lo[s], hi[s]] (clamped to 0 .. 49; null lo / hi: the full range), first index on ties.  With
+ *                            seg (S*N) int32 the counts are ADDED (int32, integer atomics: exact in any order) into
+ *                            shape_iu (S, 2, 50) = per shape and label l of its range |pred = l and seg = l|, |pred = l or seg = l|;
+ *                            shape_correct (S) = |pred = seg|; part_seen (50) = |seg = l|, part_correct (50) = |pred = seg = l|.
+ *                            Null seg: no counts.  y, scale, shift, W3 16-byte aligned.                                         */
+int pdae_partseg_supported(int G, int C, int K, int P);
+int pdae_partseg_token_pool(int B, int G, int C, const float* F, float* out, pdae_stream_t stream);
+int pdae_partseg_propagate(int B, int N, int G, int C, const float* pts, const float* centres, const float* T,
+                           const float* W0x, const float* scale0, const float* shift0, float* a0,
+                           int32_t* idx3 /*nullable*/, pdae_stream_t stream);
+int pdae_partseg_cloud_bias_relu(int B, int N, int C, float* y, const float* gbias, pdae_stream_t stream);
+int pdae_partseg_tail(int S, int N, int K, int P, const float* y, const float* scale, const float* shift, const float* W3,
+                      const float* b3, const int32_t* seg /*nullable*/, const int32_t* lo /*nullable*/,
+                      const int32_t* hi /*nullable*/, float* logp, int32_t* pred, int32_t* shape_iu /*with seg*/,
+                      int32_t* shape_correct, int32_t* part_seen, int32_t* part_correct, pdae_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Measurement aids: box calibration for bench.py (csrc/calib.hip). They replace nothing of the reference; the training
  * step never calls them.  MI355X boxes differ by +-4 % on the step and by up to 12 % on matrix loops (the clock a device
  * holds under load), so a bench line carries the rates of two kernels of known work next to its headline.

@@ -887,3 +887,116 @@ class ModelNetFewShot:
             item = order[i * self.bs:(i + 1) * self.bs]
             perm = torch.rand((self.bs, P), generator=self.gen, device=dev).argsort(1).to(torch.int32)
             yield 'ModelNet', 'sample', (item.to(torch.int32), perm, self.labels.index_select(0, item))
+
+
+def read_shapenetpart(root, split):
+    """The file list of segmentation/dataset.py:65-122 (PartNormalDataset.__init__) -> (categories [(name, directory)] in
+    the order of synsetoffset2category.txt, items [(category index, path)] category by category, file names sorted)."""
+    import json
+    cats = []
+    with open(os.path.join(root, 'synsetoffset2category.txt')) as f:
+        for line in f:
+            ls = line.strip().split()
+            if ls:
+                cats.append((ls[0], ls[1]))
+    ids = {}
+    for part in ('train', 'val', 'test'):
+        with open(os.path.join(root, 'train_test_split', 'shuffled_%s_file_list.json' % part)) as f:
+            ids[part] = set(str(d.split('/')[2]) for d in json.load(f))
+    wanted = {'trainval': ids['train'] | ids['val'], 'train': ids['train'], 'val': ids['val'], 'test': ids['test']}
+    if split not in wanted:
+        raise ValueError('ShapeNetPart: unknown split %r (trainval, train, val, test)' % (split,))
+    items = []
+    for k, (_, directory) in enumerate(cats):
+        for fn in sorted(os.listdir(os.path.join(root, directory))):
+            if fn[0:-4] in wanted[split]:
+                items.append((k, os.path.join(root, directory, os.path.splitext(fn)[0] + '.txt')))
+    return cats, items
+
+
+def synthetic_part_shapes(count, npoints, seed):
+    """The stand-in of ShapeNetPart: `count` seeded shapes in the unit ball (synthetic.labelled_clouds' primitives), each
+    of npoints .. 1.25 npoints points; the categories are drawn as shuffled rounds of the 16, so every 16 consecutive
+    shapes cover them all; part labels inside the category's range by a geometric rule -- equal slabs along x -- so any
+    point's label, seg[i, 0] included, identifies the category.  -> (clouds [(P_i, 3) f32], cls (count,) i64, segs [(P_i,) i32])."""
+    from .partseg_ops import label_tables
+    _, lo, hi = label_tables()
+    rng = np.random.default_rng(seed)
+    rounds = -(-count // len(lo))
+    cls = np.concatenate([rng.permutation(len(lo)) for _ in range(rounds)])[:count].astype(np.int64)
+    clouds, segs = [], []
+    for i in range(count):
+        P = int(rng.integers(npoints, npoints + npoints // 4 + 1))
+        x, _ = labelled_clouds(1, P, seed=int(rng.integers(1 << 31)), classes=3)
+        x = x[0]
+        n = int(hi[cls[i]] - lo[cls[i]] + 1)
+        t = (x[:, 0] - x[:, 0].min()) / max(float(x[:, 0].max() - x[:, 0].min()), 1e-12)
+        segs.append((lo[cls[i]] + np.minimum((t * n).astype(np.int32), n - 1)).astype(np.int32))
+        clouds.append(x)
+    return clouds, cls, segs
+
+
+@DATASETS.register_module()
+class ShapeNetPart:
+    """Shapes with per-point part labels for part segmentation (segmentation/dataset.py:65-167 PartNormalDataset of the
+    reference yields (point_set (npoints, 3), cls (1,), seg (npoints,))), resident on the device as ONE ragged buffer --
+    points (sum P_i, 3) f32, seg (sum P_i,) i32 -- plus offsets; batches of `bs`: (points (B, N, 3), cls (B,) i64,
+    seg (B, N) i32).  Splits trainval / train / val / test (`subset`).  Columns 0:3 and the last column of every file
+    are read (normals are not), pc_normalize is applied once per shape at load (a pure function of the stored shape:
+    what the reference computes on every access).  Per access the reference's np.random.choice(P_i, npoints,
+    replace=True) is drawn on the host generator and the gather runs on the device; the reference draws inside its
+    loader's worker processes, so the distribution is matched, not its draws.  Every shape in file order, the short last
+    batch kept.  Where DATA_PATH does not exist: synthetic_part_shapes (`count` of them)."""
+
+    def __init__(self, config):
+        self.npoints = int(config.get('npoints', 2048))
+        self.bs = int(config.get('bs', 16))
+        self.subset = config.get('subset', 'test')
+        self.device = config.get('device', 'cuda')
+        self.seed = int(config.get('seed', 0))
+        root = config.get('DATA_PATH')
+        self.listed = bool(root) and os.path.isdir(str(root))
+        if self.listed:
+            self.categories, items = read_shapenetpart(str(root), self.subset)
+            count = config.get('count', None)
+            if count is not None:
+                items = items[:int(count)]
+            clouds, segs = [], []
+            for _, path in items:
+                data = np.loadtxt(path, ndmin=2).astype(np.float32)
+                clouds.append(pc_normalize(data[:, 0:3]).astype(np.float32))
+                segs.append(data[:, -1].astype(np.int32))
+            cls = np.array([k for k, _ in items], np.int64)
+            self.paths = [p for _, p in items]
+            self.source = '%s (%s: %d shapes of %d categories)' % (root, self.subset, len(items), len(self.categories))
+        else:
+            self.source = 'synthetic stand-in (no %s)' % (root if root else 'DATA_PATH')
+            clouds, cls, segs = synthetic_part_shapes(int(config.get('count', 64)), self.npoints,
+                                                      self.seed + {'test': 2000, 'val': 3000}.get(self.subset, 1000))
+        self.count = len(clouds)
+        self.offsets = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+        cat = (lambda parts, shape: np.concatenate(parts) if parts else np.zeros(shape, np.float32))
+        self.points = torch.from_numpy(np.ascontiguousarray(cat(clouds, (0, 3)), np.float32)).to(self.device)
+        self.seg = torch.from_numpy(np.ascontiguousarray(cat(segs, (0,))).astype(np.int32)).to(self.device)
+        self.cls = torch.from_numpy(cls).to(self.device)
+        self.rng = np.random.default_rng(self.seed + 29)
+
+    def __len__(self):
+        return (self.count + self.bs - 1) // self.bs
+
+    def draw(self, items):
+        """The per-access resampling of `items`: flat rows (len(items), npoints) int64 into the ragged buffer, host."""
+        rows = np.empty((len(items), self.npoints), np.int64)
+        for j, i in enumerate(items):
+            P = int(self.offsets[i + 1] - self.offsets[i])
+            rows[j] = self.offsets[i] + self.rng.choice(P, self.npoints, replace=True)
+        return rows
+
+    def __iter__(self):
+        for i in range(0, self.count, self.bs):
+            items = range(i, min(i + self.bs, self.count))
+            rows = torch.from_numpy(self.draw(items)).to(self.points.device)
+            flat = rows.reshape(-1)
+            pts = self.points.index_select(0, flat).reshape(len(items), self.npoints, 3)
+            seg = self.seg.index_select(0, flat).reshape(len(items), self.npoints)
+            yield 'ShapeNetPart', i, (pts, self.cls[i:i + len(items)], seg)

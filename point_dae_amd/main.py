@@ -4,6 +4,7 @@ classification fine-tuning runner (--so3_rotation: its rotation-robustness proto
 evaluation of the frozen encoder; --task_affinity: the linear probe whose test loss ranks corruptions; --vote: a ten-vote
 validation behind a high plain one; --way/--shot/--fold: one fold of few-shot fine-tuning), or with --test --ckpts the
 evaluation of a fine-tuned checkpoint: the plain accuracy, then --vote_rounds rounds of ten-vote evaluation; or with
+--part_seg --test --ckpts the part-segmentation evaluation of a segmentation checkpoint on ShapeNetPart; or with
 --vis_saliency --ckpts its saliency maps: the gradient of the score with respect to every input point of the test set."""
 import torch
 
@@ -34,6 +35,10 @@ def main(argv=None):
         print('args.way : %d' % args.way)
         print('args.shot : %d' % args.shot)
         print('args.fold : %d' % args.fold)
+    if args.part_seg and args.launcher != 'none':
+        raise NotImplementedError('--part_seg runs in one process: --launcher none')
+    if args.part_seg and not args.test:
+        raise NotImplementedError('part-segmentation training is not built')
     args.use_gpu = torch.cuda.is_available()
     if not args.use_gpu:
         raise RuntimeError('point_dae_amd needs an MI355X: there is no CPU path')
@@ -74,7 +79,9 @@ def main(argv=None):
     config.dataset.train.others.bs = config.total_bs // args.world_size
     set_random_seed(args.seed + args.local_rank, deterministic=args.deterministic)   # main.py:78-81
     apply_fewshot_args(args, config)                                                 # main.py:85-91
-    if args.test:
+    if args.part_seg:
+        runner_finetune.part_seg_test(args, config)                        # segmentation/main.py:231-298
+    elif args.test:
         runner_finetune.test_net(args, config)                             # main.py:94-95
     elif args.vis_saliency:
         runner_finetune.vis_saliency_map(args, config)                     # main.py:96-97

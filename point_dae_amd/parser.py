@@ -36,6 +36,8 @@ def get_args(argv=None):
                    help='linear-SVM evaluation of the frozen encoder: SVC(kernel=linear) for C = 1e-3 .. 1e2')
     p.add_argument('--task_affinity', action='store_true', default=False,
                    help='evaluate task affinity with pre-trained encoder.')
+    p.add_argument('--part_seg', action='store_true', default=False,
+                   help='part segmentation on ShapeNetPart; with --test --ckpts <segmentation checkpoint>: its evaluation')
     p.add_argument('--way', type=int, default=-1, help='few-shot fine-tuning: classes of the episode (5 or 10)')
     p.add_argument('--shot', type=int, default=-1, help='few-shot fine-tuning: training clouds per class (10 or 20)')
     p.add_argument('--fold', type=int, default=-1, help='few-shot fine-tuning: which of the ten episodes (0-9)')
@@ -50,7 +52,7 @@ def get_args(argv=None):
     args = p.parse_args(argv)
     if args.test and args.resume:
         raise ValueError('--test and --resume cannot be both activate')
-    if args.test and args.ckpts is None:
+    if args.test and args.ckpts is None and not (args.part_seg and args.scratch_model):
         raise ValueError('ckpts shouldnt be None while test mode')
     if args.vis_saliency and args.ckpts is None:
         raise ValueError('ckpts shouldnt be None while vis_saliency mode')

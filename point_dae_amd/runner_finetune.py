@@ -23,6 +23,10 @@ are counted on the device and test_net reads its rounds' counters once.
 vis_saliency_map (:751-833, main.py --vis_saliency) differentiates a fine-tuned classifier's score with respect to its
 input points over the test set, a batch at a time (saliency_ops), and saves the reference's (n, npoints, 6) tensor.
 
+part_seg_test (segmentation/main.py:231-298, main.py --part_seg --test) evaluates a segmentation checkpoint on ShapeNetPart:
+one evaluation pass of part_seg.PointTransformerPartSeg, the metric's integer counts on the device (partseg_ops), one
+read-back, the reference's mIoU lines.
+
 Few-shot fine-tuning (main.py --way/--shot/--fold, datasets.ModelNetFewShot) is run_net on one resident episode: the
 train loader yields the draws of a batch (items, a fresh point shuffle per row) and fewshot_train_points makes the step's
 input of them -- fewshot_ops (csrc/fewshot.hip): one launch --; the test loader's FPS-to-npoints point sets are taken once
@@ -310,6 +314,43 @@ def test_net(args, config, log=print):
         acc = max(accs)
     log('[TEST_VOTE] acc = %.4f' % acc)
     return acc
+
+
+@torch.no_grad()
+def part_seg_test(args, config, log=print):
+    """segmentation/main.py:231-298 of the reference (main.py --part_seg --test): one pass over the `test` split of
+    ShapeNetPart with a segmentation checkpoint (model.load_segmentation_checkpoint(args.ckpts); --scratch_model in
+    place of --ckpts: the initial weights) in evaluation mode.  Every shape's prediction is the argmax over its own
+    part range, taken from its first point's label; the metric's integer counts stay on the device
+    (partseg_ops.Counts) and are read ONCE behind the last batch; the host forms accuracy, class_avg_accuracy, the
+    per-category mIoU, class_avg_iou and inctance_avg_iou in float64 and prints the reference's lines.  -> the
+    instance mIoU; the four metrics are left in args.part_seg_metrics."""
+    from . import partseg_ops
+    if getattr(args, 'distributed', False) or getattr(args, 'launcher', 'none') != 'none':
+        raise NotImplementedError('--part_seg runs in one process: --launcher none')
+    device = torch.device('cuda', torch.cuda.current_device())
+    log('Tester start ... ')
+    test_loader = _loader(config.dataset.test, device, args.seed, 0, 1, config.total_bs)
+    log('ShapeNetPart test source: %s' % test_loader.source)
+    base_model = builder.model_builder(config.model)
+    if args.ckpts is not None:
+        base_model.load_segmentation_checkpoint(args.ckpts, log=log)
+    elif getattr(args, 'scratch_model', False):
+        base_model.load_model_from_ckpt(None, log=log)
+    else:
+        raise ValueError('ckpts shouldnt be None while test mode')
+    base_model = base_model.to(device).eval()
+    log('Part-segmentation backend: %s' % partseg_ops.mode())
+    counts = partseg_ops.Counts(test_loader.count, device)
+    for _, _, (points, cls, seg) in test_loader:
+        base_model(points, cls, seg=seg, counts=counts)
+    m = partseg_ops.metrics(counts.read())                              # the test's one read-back
+    for cat in sorted(m['category_iou']):
+        log('eval mIoU of %s %f' % (cat + ' ' * (14 - len(cat)), m['category_iou'][cat]))
+    log('test Accuracy: %f  Class avg mIOU: %f   Inctance avg mIOU: %f'
+        % (m['accuracy'], m['class_avg_iou'], m['inctance_avg_iou']))
+    args.part_seg_metrics = m
+    return m['inctance_avg_iou']
 
 
 def vis_saliency_map(args, config, log=print):
