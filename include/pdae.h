@@ -572,6 +572,32 @@ int pdae_sa_eval_forward(int B, int N, int np, int ns, int C0, int C1, int C2, i
                          const float* shift1, const float* W2, const float* scale2, const float* shift2, float* out,
                          pdae_stream_t stream);
 
+/* The FIRST layer of a set-abstraction level in TRAINING mode, split by source point (csrc/sa_train.hip): the identity of
+ * sa_eval_forward's layer 0 with batch statistics, forward and backward.  No (B np ns, 4 + C0) grouped tensor exists.
+ *   sa_first_forward:  y0[row, :] = P[b*N + j, :] + W0x d,  j = idx[row],  d = xyz[b,j] - new_xyz[b,p]  (row = (b, p, s);
+ *       R = B np ns rows; P (B*N, C1) = features . W0f^T from the caller, NULL exactly when C0 == 0; W0x (C1, 3)), the raw
+ *       conv output the level's next pdae_conv_stats reads, and stats [8][2][C1], the partial column sums of y0 and y0^2
+ *       in the layout pdae_conv_stats writes (-> pdae_bn_finalize with P = 8).
+ *   sa_first_backward: dy0 (R, C1) the gradient of y0 ->
+ *       dP[b*N + j, :] = the sum of dy0[row, :] over the rows of cloud b whose idx is j, in ascending row order (fully
+ *           written; NULL exactly when C0 == 0), from which the caller takes dW0f = dP^T features and dfeatures = dP W0f;
+ *       dW0x[c, k]     = sum over the rows of dy0[row, c] * d[row, k].
+ * Fixed summation order throughout (block partials in `workspace`, added in block order; no float atomics): the same bits
+ * on every run.  An index outside [0, N) is clamped.  workspace: sa_first_forward_workspace / _backward_workspace floats.
+ * sa_first_supported: 1 when the kernels take the layout -- ns 32 or 64, C0 and C1 multiples of 4, C1 / 4 a divisor of
+ * 256, and with C0 > 0 (a dP to form) N <= 4096 and 4 (2 N + 1 + 2 np ns) <= 150 KB, the sort of a cloud's rows in LDS --
+ * else 0; both entries return PDAE_ERR_UNSUPPORTED for every other layout before anything is read or launched.
+ * P, y0, dy0, dP and the workspace 16-byte aligned. */
+int pdae_sa_first_supported(int B, int N, int np, int ns, int C0, int C1);
+long long pdae_sa_first_forward_workspace(long long R, int C1);
+long long pdae_sa_first_backward_workspace(long long R, int C1);
+int pdae_sa_first_forward(int B, int N, int np, int ns, int C0, int C1, const float* xyz, const float* new_xyz,
+                          const int32_t* idx, const float* P /*nullable, C0 = 0*/, const float* W0x, float* y0, float* stats,
+                          float* workspace, pdae_stream_t stream);
+int pdae_sa_first_backward(int B, int N, int np, int ns, int C0, int C1, const float* xyz, const float* new_xyz,
+                           const int32_t* idx, const float* dy0, float* dP /*nullable, C0 = 0*/, float* dW0x,
+                           float* workspace, pdae_stream_t stream);
+
 /* First layer of the FoldingNet stage of Point_CAE_PointNetv2 (csrc/folding.hip;
  * models/PointCAE_pointnetv2.py:157-167: folding2[0] over [grid(2) | coarse point(3) |
  * global feature(1024)] for `cells` grid cells x `coarse` points x `clouds`).  The

@@ -19,6 +19,7 @@ once per coarse point and once per cloud and added by broadcasting -- the same
 sum, 25.9 -> 8.7 GFLOP per cloud.
 """
 import itertools
+import os
 
 import numpy as np
 import torch
@@ -103,12 +104,16 @@ class _GroupRows(torch.autograd.Function):
 class PointnetSAModule(nn.Module):
     """FPS -> ball query -> group (centre-subtracted xyz || features) -> shared MLP -> max.
     fused_eval: in evaluation mode take the forward-only level of sa_eval_ops (PDAE_SA_EVAL=hip, the default) where it
-    takes the layout; off (the default), and in training mode, forward is untouched by it."""
+    takes the layout; off (the default), and in training mode, forward is untouched by it.
+    split_first: in training mode run the first layer split by source point (sa_mlp.SplitFirstMLPMaxFunction: no grouped
+    rows) where csrc/sa_train.hip takes the layout, the grouped form elsewhere; off (the default): the grouped form, untouched.
+    A group-all level has every point once, so the switch does nothing there."""
 
-    def __init__(self, mlp, npoint=None, radius=None, nsample=None, use_xyz=True, fused_eval=False):
+    def __init__(self, mlp, npoint=None, radius=None, nsample=None, use_xyz=True, fused_eval=False, split_first=False):
         super().__init__()
         self.npoint, self.radius, self.nsample = npoint, radius, nsample
         self.fused_eval = bool(fused_eval) and use_xyz
+        self.split_first = bool(split_first) and use_xyz and npoint is not None
         spec = list(mlp)
         if use_xyz:
             spec[0] += 3
@@ -116,7 +121,8 @@ class PointnetSAModule(nn.Module):
 
     def forward(self, xyz, features=None, capture=None):
         """xyz (B,N,3); features rows (B*N, C) or None -> new_xyz (B,np,3), rows (B*np, C').  capture: a dict that
-        receives the level's FPS and ball-query indices (tests)."""
+        receives the level's FPS and ball-query indices and, from a split_first level in training mode, which form of
+        the first layer ran ('first': 'split' or 'grouped') (tests)."""
         B, N, _ = xyz.shape
         fused = self.fused_eval and not self.training and sa_eval_ops.mode() == 'hip'
         if self.npoint is not None:
@@ -130,6 +136,14 @@ class PointnetSAModule(nn.Module):
                 if out is not None:              # (None: a layout the kernel refuses -- the layer-by-layer form below)
                     return new_xyz, out
             C = 0 if features is None else features.shape[1]
+            if self.split_first and self.training:
+                layers = list(self.mlps[0])
+                split = (sa_mlp.split_first_supported(B, N, self.npoint, self.nsample, C, layers[0].conv.out_channels)
+                         and not any(isinstance(layer.bn.bn, nn.SyncBatchNorm) for layer in layers))
+                if capture is not None:
+                    capture['first'] = 'split' if split else 'grouped'
+                if split:                        # (else: a layout the kernels refuse -- the grouped form below)
+                    return new_xyz, sa_mlp.split_first_mlp_max(xyz, new_xyz, idx, features, layers)
             if (C % 4 == 0 and C <= 1024 and N <= 4096 and
                     4 * (2 * N + 1 + self.npoint * self.nsample) <= 150 * 1024):     # (a cloud's sort lives in LDS)
                 g = _GroupRows.apply(xyz, new_xyz, idx, features)      # xyz - centre | 0 | features: K a multiple of 4
@@ -159,10 +173,12 @@ class PointnetSAModule(nn.Module):
 
 
 class PointNetv2_encoder(nn.Module):
-    def __init__(self, num_channel=3, fused_eval=False):
+    def __init__(self, num_channel=3, fused_eval=False, split_first=False):
         super().__init__()
-        self.sa1 = PointnetSAModule(npoint=512, radius=0.2, nsample=32, mlp=[0, 64, 64, 128], fused_eval=fused_eval)
-        self.sa2 = PointnetSAModule(npoint=128, radius=0.4, nsample=64, mlp=[128, 128, 128, 256], fused_eval=fused_eval)
+        self.sa1 = PointnetSAModule(npoint=512, radius=0.2, nsample=32, mlp=[0, 64, 64, 128], fused_eval=fused_eval,
+                                    split_first=split_first)
+        self.sa2 = PointnetSAModule(npoint=128, radius=0.4, nsample=64, mlp=[128, 128, 128, 256], fused_eval=fused_eval,
+                                    split_first=split_first)
         self.sa3 = PointnetSAModule(mlp=[256, 256, 512, 1024], fused_eval=fused_eval)
 
     def forward(self, xyz, capture=None):
@@ -172,6 +188,8 @@ class PointNetv2_encoder(nn.Module):
         _, l3 = self.sa3(l2_xyz, l2)
         if capture is not None:
             capture.update(fps_idx=[c['fps_idx'] for c in caps], ball_idx=[c['ball_idx'] for c in caps], levels=[l1, l2])
+            if any('first' in c for c in caps):
+                capture['first'] = [c.get('first') for c in caps]
         return l3                                                  # (B, 1024)
 
 
@@ -267,6 +285,69 @@ class PointNetv2_feat(Classifier):
             raise RuntimeError('PointNetv2_feat: points must be on the GPU (there is no CPU path)')
         begin_step(pts.device)
         f = self.pointnetv2_encoder(pts[:, :, :3].contiguous(), capture)
+        if capture is not None:
+            capture.update(feature=f)
+        return f
+
+
+# measured on the graphed fine-tuning step at B = 32 (tools/bench_pointnetv2_cls.py): split 3.84 ms against
+# grouped 4.14 at N = 1024, 3.99 against 4.27 at N = 2048; the spread of grouped is 0.04 and 0.07
+SA_FIRST_DEFAULT = 'split'
+
+
+def sa_first_mode():
+    """PDAE_SA_FIRST: how the classifier's sa1 and sa2 run their first layer in training mode -- 'split' (by source point,
+    sa_mlp.SplitFirstMLPMaxFunction) or 'grouped' (_GroupRows + sa_mlp.SharedMLPMaxFunction, the pretraining step's form:
+    the fallback for the layouts the split kernels refuse, and the A/B and timing baseline)."""
+    mode = os.environ.get('PDAE_SA_FIRST', '') or SA_FIRST_DEFAULT
+    if mode not in ('split', 'grouped'):
+        raise ValueError("PDAE_SA_FIRST must be 'split' or 'grouped', got %r" % mode)
+    return mode
+
+
+@MODELS.register_module()
+class PointNetv2(Classifier):
+    """models/PointCAE_pointnetv2.py:749-842: the PointNet++ encoder of a Point_CAE_PointNetv2 checkpoint fine-tuned as a
+    classifier.  pointnetv2_encoder is the auto-encoder's module under the same name, so its checkpoint loads with
+    folding1.* / folding2.* unexpected and cls_head_finetune.* missing; the head Linear(1024, 512) -> BatchNorm1d -> ReLU ->
+    Dropout(0.5) -> Linear(512, 256) -> BatchNorm1d -> ReLU -> Dropout(0.5) -> Linear(256, cls_dim) runs on
+    Classifier.head.  get_loss_acc, load_model_from_ckpt and _init_weights are the classifier's.
+
+    Evaluation mode runs the fused levels of sa_eval_ops, as PointNetv2_feat does; training mode runs sa1 and sa2 as
+    PDAE_SA_FIRST says (sa_first_mode, read here) and sa3, the group-all level, in the grouped form.  There is no CPU path."""
+
+    # parameters whose gradients backward produces last (FlatDataParallel lays them at the end of the flat buffer)
+    late_grad_prefixes = ('pointnetv2_encoder.sa1.',)
+    input_grad_supported = False
+    only_new_unsupported = ("set_bn_eval freezes every BatchNorm whose width is not 256, which leaves pointnetv2_encoder.sa2's "
+                            "last and sa3's first BatchNorm (256 channels) in training mode beside frozen ones; the clip norm "
+                            "is taken over the whole gradient, so the protocol needs an encoder backward through that mix of "
+                            "batch-statistics and running-estimate BatchNorms, and the set-abstraction levels' autograd nodes "
+                            "differentiate training-mode BatchNorm only")
+
+    def __init__(self, config, **kwargs):
+        super().__init__()
+        self.config = config
+        self.cls_dim = config.cls_dim
+        self.smoothing = bool(config.get('smoothloss', False))
+        if not 2 <= self.cls_dim <= 64:
+            raise NotImplementedError('PointNetv2: cls_dim = %d; the loss kernels take 2 to 64 classes' % self.cls_dim)
+        self.sa_first = sa_first_mode()
+        self.pointnetv2_encoder = PointNetv2_encoder(fused_eval=True, split_first=self.sa_first == 'split')
+        self.cls_head_finetune = nn.Sequential(
+            nn.Linear(1024, 512), nn.BatchNorm1d(512), nn.ReLU(inplace=True), nn.Dropout(0.5),
+            nn.Linear(512, 256), nn.BatchNorm1d(256), nn.ReLU(inplace=True), nn.Dropout(0.5),
+            nn.Linear(256, self.cls_dim))
+
+    @property
+    def smooth_eps(self):
+        """get_loss_acc's label smoothing (the reference's PointNetv2.get_loss_acc): eps 0.3 with smoothloss, else
+        F.cross_entropy."""
+        return SMOOTH_EPS if self.smoothing else None
+
+    def trunk(self, pts, capture):
+        """pts (B, N, 3) -> the encoder's feature (B, 1024) (PointCAE_pointnetv2.py:833-840)."""
+        f = self.pointnetv2_encoder(pts, capture)
         if capture is not None:
             capture.update(feature=f)
         return f

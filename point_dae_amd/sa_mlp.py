@@ -22,7 +22,7 @@ ATen ran ~7 passes per layer forward (stats, transform, clamp) and ~6 backward.
 import torch
 
 from . import _lib
-from .rows import bn_finalize, empty, gemm_bnstats, insert_zero_col, rows_gemm, rows_wgrad, wgrad_listed
+from .rows import _hcat, bn_finalize, empty, gemm_bnstats, insert_zero_col, rows_gemm, rows_wgrad, wgrad_listed
 
 
 # Parity-test hook (None in production): called as ARG_HOOK(arg) with the (groups, C) uint8 winners of a level's
@@ -116,6 +116,144 @@ class SharedMLPMaxFunction(torch.autograd.Function):
                 if ctx.needs_input_grad[0]:
                     dx = rows_gemm(d, ws[0], True)
         return (dx, None, None) + tuple(grads)
+
+
+def split_first_supported(B, N, npoint, ns, C0, C1):
+    """Whether csrc/sa_train.hip takes a level's layout (host-side query, nothing is read)."""
+    return bool(_lib.lib().pdae_sa_first_supported(B, N, npoint, ns, C0, C1))
+
+
+class SplitFirstMLPMaxFunction(torch.autograd.Function):
+    """SharedMLPMaxFunction without the grouped rows: the level's first layer split by source point (csrc/sa_train.hip).
+
+        y0[row] = P[b N + idx[row]] + W0x (xyz[idx[row]] - new_xyz[centre]),    P = features W0f^T on B N rows
+
+    The feature half of the first product runs once per SOURCE point (sa2: B 512 rows instead of B 128 64) and only three
+    FMAs on the centred difference stay per (centre, sample) row; no (R, 4 + C0) tensor is built.  From y0 on the chain is
+    SharedMLPMaxFunction's own (conv_stats / bn_finalize / bnrelu_group_max; its backward down to dy0).  Then one entry
+    turns dy0 into dP (per source point, ascending row order) and dW0x, and dW0f = dP^T features, dfeatures = dP W0f are
+    products on B N rows."""
+
+    @staticmethod
+    def forward(ctx, xyz, new_xyz, idx, features, bns, *params):
+        """xyz (B,N,3), new_xyz (B,np,3), idx (B,np,ns) i32, features (B*N, C0) or None; params = (w, gamma, beta) per layer,
+        the first w (C1, 3 + C0) as the module holds it."""
+        B, N, _ = xyz.shape
+        _, npoint, ns = idx.shape
+        xyz, new_xyz, idx = xyz.contiguous(), new_xyz.contiguous(), idx.contiguous()
+        C0 = 0 if features is None else features.shape[1]
+        w0 = params[0]
+        C1 = w0.shape[0]
+        if w0.shape[1] != 3 + C0:
+            raise RuntimeError('split first layer: the first weight must be (C1, 3 + feature width)')
+        R = B * npoint * ns
+        w0x = w0[:, :3].contiguous()
+        w0f = feats = P = None
+        if C0:
+            w0f, feats = w0[:, 3:].contiguous(), features.contiguous()
+            P = rows_gemm(feats, w0f)                                       # (B*N, C1), once per source point
+        ws = [None] + [params[i].contiguous() for i in range(3, len(params), 3)]
+        gammas = [params[i] for i in range(1, len(params), 3)]
+        y0 = empty((R, C1), xyz)
+        stats = empty((8, 2, C1), xyz)
+        wsp = empty((max(_lib.lib().pdae_sa_first_forward_workspace(R, C1), 4),), xyz)
+        _lib.call('pdae_sa_first_forward', xyz, B, N, npoint, ns, C0, C1, _lib.ptr(xyz), _lib.ptr(new_xyz), _lib.ptr(idx),
+                  _lib.ptr(P), _lib.ptr(w0x), _lib.ptr(y0), _lib.ptr(stats), _lib.ptr(wsp))
+        del P, wsp
+        sc, sh, mean, invstd = bn_finalize(bns[0], R, xyz, partials=stats)
+        ys, affs = [y0], [(sc, sh, mean, invstd)]
+        inp = y0
+        for w, bn in zip(ws[1:], bns[1:]):
+            Nl, K = w.shape
+            y = empty((R, Nl), xyz)
+            stats = empty((8, 2, Nl), xyz)
+            _lib.call('pdae_conv_stats', xyz, R, Nl, K, _lib.ptr(inp), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(w),
+                      _lib.ptr(y), _lib.ptr(stats))
+            sc, sh, mean, invstd = bn_finalize(bn, R, xyz, partials=stats)
+            ys.append(y)
+            affs.append((sc, sh, mean, invstd))
+            inp = y
+        G, C = R // ns, ys[-1].shape[1]
+        out = empty((G, C), xyz)
+        arg = empty((G, C), xyz, torch.uint8)
+        _lib.call('pdae_bnrelu_group_max', xyz, G, ns, C, _lib.ptr(inp), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(out),
+                  _lib.ptr(arg))
+        if ARG_HOOK is not None:
+            arg = ARG_HOOK(arg).contiguous()
+        ctx.save_for_backward(xyz, new_xyz, idx, feats, w0f, arg, out, *ws[1:], *gammas, *ys, *[t for a in affs for t in a])
+        ctx.dims, ctx.nl = (B, N, npoint, ns, C0, C1), len(ys)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        t = ctx.saved_tensors
+        nl = ctx.nl
+        B, N, npoint, ns, C0, C1 = ctx.dims
+        xyz, new_xyz, idx, feats, w0f, arg, out = t[:7]
+        t = t[7:]
+        ws = (None,) + tuple(t[:nl - 1])
+        gammas, ys = t[nl - 1:2 * nl - 1], t[2 * nl - 1:3 * nl - 1]
+        flat = t[3 * nl - 1:]
+        affs = [flat[4 * i:4 * i + 4] for i in range(nl)]
+        x = xyz
+        R = B * npoint * ns
+        G, C = R // ns, ys[-1].shape[1]
+        grads = [None] * (3 * nl)
+        dfeat = None
+        d = empty((R, C), x)
+        dout = dout.contiguous()
+        fused_pool = 256 % (C // 4) == 0 and C <= 1024
+        if not fused_pool:
+            _lib.call('pdae_group_max_scatter_n', x, G, ns, C, _lib.ptr(dout), _lib.ptr(arg), _lib.ptr(d))
+        S_pre = None
+        for l in range(nl - 1, -1, -1):
+            sc, sh, mean, invstd = affs[l]
+            Nl = ys[l].shape[1]
+            S = empty((2, Nl), x) if S_pre is None else S_pre
+            if S_pre is not None:
+                _lib.call('pdae_bnrelu_backward_apply', x, R // 32, Nl, _lib.ptr(d), _lib.ptr(ys[l]), _lib.ptr(sc),
+                          _lib.ptr(sh), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(gammas[l]), _lib.ptr(S), None,
+                          R // 32, None, None, None)
+            elif l == nl - 1 and fused_pool:
+                wsp = empty((max(_lib.lib().pdae_pool_bn_backward_workspace(G, C), 1),), x)
+                _lib.call('pdae_pool_bn_backward', x, G, ns, C, _lib.ptr(dout), _lib.ptr(arg), _lib.ptr(out),
+                          _lib.ptr(ys[l]), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(gammas[l]), _lib.ptr(S),
+                          _lib.ptr(wsp), _lib.ptr(d))
+            else:
+                _lib.call('pdae_bnrelu_backward', x, R // 32, Nl, _lib.ptr(d), _lib.ptr(ys[l]), _lib.ptr(sc),
+                          _lib.ptr(sh), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(gammas[l]), _lib.ptr(S), None,
+                          R // 32, None, None, None)
+            grads[3 * l + 1], grads[3 * l + 2] = S[1], S[0]                   # dgamma, dbeta
+            if l > 0:
+                psc, psh = affs[l - 1][0], affs[l - 1][1]
+                grads[3 * l] = wgrad_listed(R, d, None, ys[l - 1], None, psc, psh)[0]
+                d, S_pre = gemm_bnstats(d, ws[l], ys[l - 1], None, psc, psh, affs[l - 1][2], affs[l - 1][3])
+            else:
+                # d is dy0: per source point and against the centred differences, then products on B*N rows
+                dP = empty((B * N, C1), x) if C0 else None
+                dw0x = empty((C1, 3), x)
+                wsp = empty((max(_lib.lib().pdae_sa_first_backward_workspace(R, C1), 4),), x)
+                _lib.call('pdae_sa_first_backward', x, B, N, npoint, ns, C0, C1, _lib.ptr(xyz), _lib.ptr(new_xyz),
+                          _lib.ptr(idx), _lib.ptr(d), _lib.ptr(dP), _lib.ptr(dw0x), _lib.ptr(wsp))
+                if C0:
+                    (dw0f,), _ = rows_wgrad([dP], [feats], [False])
+                    grads[0] = _hcat([(dw0x, 3), (dw0f, C0)], C1, x)
+                    if ctx.needs_input_grad[3]:
+                        dfeat = rows_gemm(dP, w0f, True)
+                else:
+                    grads[0] = dw0x
+        return (None, None, None, dfeat, None) + tuple(grads)
+
+
+def split_first_mlp_max(xyz, new_xyz, idx, features, layers):
+    """A level's shared MLP + max-pool with the first layer split by source point -> (B*np, C_last).  layers: the level's
+    _ConvBN modules; the caller has asked split_first_supported."""
+    params, bns = [], []
+    for layer in layers:
+        bn = layer.bn.bn
+        params += [layer.conv.weight.reshape(layer.conv.weight.shape[0], -1), bn.weight, bn.bias]
+        bns.append(bn)
+    return SplitFirstMLPMaxFunction.apply(xyz, new_xyz, idx, features, bns, *params)
 
 
 def shared_mlp_max(x, layers, ns, pad_at=None):
