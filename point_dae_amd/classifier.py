@@ -4,7 +4,8 @@ loading, weight init, the loss, and cls_head_finetune run on the HIP kernels.
 A subclass builds its trunk and a cls_head_finetune Sequential of Linear layers and, between them, blocks of
 BatchNorm1d -> ReLU or LeakyReLU [-> Dropout], and defines trunk(pts, capture) -> the feature the head takes.  The head's
 Linear layers run on the row GEMMs (rows.linear_any), each block as ONE launch (finetune_ops.bn_relu_dropout /
-bn_lrelu_dropout).  There is no CPU path.
+bn_lrelu_dropout).  There is no CPU path.  forward_features is the guard every forward shares (the refusals, the
+three-column slice, begin_step) in front of the trunk; the frozen feature extractors are trunks whose forward is that.
 """
 import logging
 
@@ -39,6 +40,9 @@ class Classifier(nn.Module):
     # whether the eval-mode model can be differentiated with respect to its input points (saliency_ops.input_gradients,
     # runner_finetune.vis_saliency_map): every link of its backward must carry a data gradient down to (B, N, 3)
     input_grad_supported = False
+    # None, or for a model that is never trained the tail of forward_features' refusal in training mode:
+    # '<class>: evaluation mode only -- <eval_only>'
+    eval_only = None
 
     # ---- the reference's helpers ------------------------------------------------------------------------------------
     def get_loss_acc(self, ret, gt):
@@ -144,10 +148,17 @@ class Classifier(nn.Module):
                 x = finetune_ops.bn_lrelu_dropout(x, bn, p, slope, u=u, keep=keep, dropout=self.training)
         return x
 
-    def forward(self, pts, drop=None, drop_keep=None, capture=None):
-        """pts (B, N, 3+) -> logits (B, cls_dim); capture: a dict the trunk fills with its intermediates (tests)."""
+    def forward_features(self, pts, capture=None):
+        """pts (B, N, 3+) -> the trunk's feature; capture: a dict the trunk fills with its intermediates (tests).  This is
+        the whole forward of a frozen feature extractor (a trunk without a head)."""
+        if self.training and self.eval_only is not None:
+            raise NotImplementedError(f'{type(self).__name__}: evaluation mode only -- {self.eval_only}')
         if not pts.is_cuda:
             raise RuntimeError(f'{type(self).__name__}: points must be on the GPU (there is no CPU path)')
         pts = pts[:, :, :3].contiguous()
         begin_step(pts.device)
-        return self.head(self.trunk(pts, capture), drop, drop_keep)
+        return self.trunk(pts, capture)
+
+    def forward(self, pts, drop=None, drop_keep=None, capture=None):
+        """pts (B, N, 3+) -> logits (B, cls_dim)."""
+        return self.head(self.forward_features(pts, capture), drop, drop_keep)

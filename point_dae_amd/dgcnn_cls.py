@@ -20,7 +20,6 @@ the linear-SVM evaluation protocol fits its classifiers on (runner_finetune.svm_
 """
 import torch.nn as nn
 
-from .arena import begin_step
 from .classifier import Classifier
 from .point_cae_dgcnn import dgcnn_encoder
 from .registry import MODELS
@@ -74,9 +73,4 @@ class DGCNN_feat(DGCNN):
         super().__init__(config, **kwargs)
         del self.cls_head_finetune
 
-    def forward(self, pts, capture=None):
-        """pts (B, N, 3+) -> the encoder's feature (B, 1024)."""
-        if not pts.is_cuda:
-            raise RuntimeError('DGCNN_feat: points must be on the GPU (there is no CPU path)')
-        begin_step(pts.device)
-        return self.trunk(pts[:, :, :3].contiguous(), capture)
+    forward = Classifier.forward_features      # pts (B, N, 3+) -> the encoder's feature (B, 1024); gradients are recorded

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, nn_ops, sa_eval_ops, sa_mlp
+from . import nn_ops, sa_eval_ops, sa_mlp
 from .arena import begin_step
 from .chamfer_dist import ChamferDistanceL1, ChamferDistanceL2
 from .classifier import Classifier
@@ -34,6 +34,7 @@ from .corrupt_util_tensor import corrupt_in_forward
 from .pointnet2_utils import ball_query, furthest_point_sample_with_centres
 from .registry import MODELS
 from .rows import linear_any, pad2d, split_weight_cols
+from .sa_mlp import _GroupRows  # noqa: F401  (its home is sa_mlp; tests import it from here)
 
 
 class _ConvBN(nn.Sequential):
@@ -71,36 +72,6 @@ class SharedMLP(nn.Sequential):
             self.add_module('layer{}'.format(i), _ConvBN(spec[i], spec[i + 1]))
 
 
-class _GroupRows(torch.autograd.Function):
-    """QueryAndGroup in row layout (pointnet2_utils.py:345-361) as one kernel each way (csrc/ball_group.hip
-    sa_group_rows*): rows [xyz - centre | 0 | features]; gradient to the features only (coordinates are inputs)."""
-
-    @staticmethod
-    def forward(ctx, xyz, new_xyz, idx, features):
-        B, N, _ = xyz.shape
-        _, npoint, ns = idx.shape
-        C = 0 if features is None else features.shape[1]
-        out = torch.empty((B * npoint * ns, 4 + C), device=xyz.device, dtype=torch.float32)
-        xyz, new_xyz, idx = xyz.contiguous(), new_xyz.contiguous(), idx.contiguous()
-        feats = features.contiguous() if features is not None else None
-        _lib.call('pdae_sa_group_rows', xyz, B, N, npoint, ns, C, _lib.ptr(xyz), _lib.ptr(new_xyz), _lib.ptr(idx),
-                  _lib.ptr(feats), _lib.ptr(out))
-        ctx.save_for_backward(idx)
-        ctx.dims = (B, N, npoint, ns, C)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        (idx,) = ctx.saved_tensors
-        B, N, npoint, ns, C = ctx.dims
-        if C == 0 or not ctx.needs_input_grad[3]:
-            return None, None, None, None
-        dout = dout.contiguous()
-        dfeat = torch.empty((B * N, C), device=dout.device, dtype=torch.float32)
-        _lib.call('pdae_sa_group_rows_grad', dout, B, N, npoint, ns, C, _lib.ptr(idx), _lib.ptr(dout), _lib.ptr(dfeat))
-        return None, None, None, dfeat
-
-
 class PointnetSAModule(nn.Module):
     """FPS -> ball query -> group (centre-subtracted xyz || features) -> shared MLP -> max.
     fused_eval: in evaluation mode take the forward-only level of sa_eval_ops (PDAE_SA_EVAL=hip, the default) where it
@@ -124,49 +95,34 @@ class PointnetSAModule(nn.Module):
         receives the level's FPS and ball-query indices and, from a split_first level in training mode, which form of
         the first layer ran ('first': 'split' or 'grouped') (tests)."""
         B, N, _ = xyz.shape
-        fused = self.fused_eval and not self.training and sa_eval_ops.mode() == 'hip'
-        if self.npoint is not None:
+        layers = list(self.mlps[0])
+        grouped = self.npoint is not None                  # (else the group-all level: one group per cloud, no centres)
+        new_xyz = idx = None
+        if grouped:
             with torch.no_grad():
                 fps_idx, new_xyz = furthest_point_sample_with_centres(xyz, self.npoint)
                 idx = ball_query(self.radius, self.nsample, xyz, new_xyz)          # (B,np,ns) i32
             if capture is not None:
                 capture.update(fps_idx=fps_idx, ball_idx=idx)
-            if fused:
-                out = sa_eval_ops.level(xyz, new_xyz, idx, features, list(self.mlps[0]))
-                if out is not None:              # (None: a layout the kernel refuses -- the layer-by-layer form below)
-                    return new_xyz, out
+        if self.fused_eval and not self.training and sa_eval_ops.mode() == 'hip':
+            out = (sa_eval_ops.level(xyz, new_xyz, idx, features, layers) if grouped else
+                   sa_eval_ops.group_all(xyz, features, layers))
+            if out is not None:                  # (None: a layout the kernel refuses -- the layer-by-layer form below)
+                return new_xyz, out
+        if self.split_first and self.training:   # (never set on a group-all level)
             C = 0 if features is None else features.shape[1]
-            if self.split_first and self.training:
-                layers = list(self.mlps[0])
-                split = (sa_mlp.split_first_supported(B, N, self.npoint, self.nsample, C, layers[0].conv.out_channels)
-                         and not any(isinstance(layer.bn.bn, nn.SyncBatchNorm) for layer in layers))
-                if capture is not None:
-                    capture['first'] = 'split' if split else 'grouped'
-                if split:                        # (else: a layout the kernels refuse -- the grouped form below)
-                    return new_xyz, sa_mlp.split_first_mlp_max(xyz, new_xyz, idx, features, layers)
-            if (C % 4 == 0 and C <= 1024 and N <= 4096 and
-                    4 * (2 * N + 1 + self.npoint * self.nsample) <= 150 * 1024):     # (a cloud's sort lives in LDS)
-                g = _GroupRows.apply(xyz, new_xyz, idx, features)      # xyz - centre | 0 | features: K a multiple of 4
-            else:                # shapes the fused kernel refuses: the index_select / cat form
-                flat = (idx.long() + torch.arange(B, device=xyz.device).view(B, 1, 1) * N).reshape(-1)
-                g = xyz.reshape(B * N, 3).index_select(0, flat).reshape(B, self.npoint, self.nsample, 3)
-                g = (g - new_xyz.unsqueeze(2)).reshape(-1, 3)
-                zero = g.new_zeros(g.shape[0], 1)
-                g = torch.cat([g, zero] + ([features.index_select(0, flat)] if features is not None else []), dim=1)
-            groups, per = B * self.npoint, self.nsample
+            split = (sa_mlp.split_first_supported(B, N, self.npoint, self.nsample, C, layers[0].conv.out_channels)
+                     and sa_mlp.batch_stats_are_local(layers))
+            if capture is not None:
+                capture['first'] = 'split' if split else 'grouped'
+            if split:                            # (else: a layout the kernels refuse -- the grouped form below)
+                return new_xyz, sa_mlp.split_first_mlp_max(xyz, new_xyz, idx, features, layers)
+        if grouped:
+            g, groups, per = sa_mlp.group_rows(xyz, new_xyz, idx, features), B * self.npoint, self.nsample
         else:
-            new_xyz = None
-            if fused:
-                out = sa_eval_ops.group_all(xyz, features, list(self.mlps[0]))
-                if out is not None:
-                    return new_xyz, out
-            g = xyz.reshape(B * N, 3)
-            g = torch.cat([g, g.new_zeros(g.shape[0], 1)] + ([features] if features is not None else []), dim=1)
-            groups, per = B, N
-        layers = list(self.mlps[0])
-        if self.training and per <= 256 and g.shape[0] % 32 == 0 and not any(
-                isinstance(layer.bn.bn, nn.SyncBatchNorm) for layer in layers):
-            return new_xyz, sa_mlp.shared_mlp_max(g, layers, per, pad_at=3)      # fused (sa_mlp.py)
+            g, groups, per = sa_mlp.all_rows(xyz.reshape(B * N, 3), features), B, N
+        if self.training and sa_mlp.fused_chain_supported(per, g.shape[0], layers):
+            return new_xyz, sa_mlp.shared_mlp_max(g, layers, per, pad_at=3)
         for i, layer in enumerate(layers):
             g = layer.rows(g, pad_at=3 if i == 0 else None)
         return new_xyz, g.reshape(groups, per, -1).max(dim=1)[0]
@@ -256,38 +212,46 @@ class Point_CAE_PointNetv2(nn.Module):
 SMOOTH_EPS = 0.3           # get_loss_acc's label smoothing (PointCAE_pointnetv2.py:950-957)
 
 
-@MODELS.register_module()
-class PointNetv2_feat(Classifier):
-    """models/PointCAE_pointnetv2.py:936-1017: the PointNet++ encoder as the frozen feature extractor of
-    --svm_classification -- pointnetv2_encoder and nothing else that carries parameters, so a Point_CAE_PointNetv2
-    checkpoint loads with folding1.* / folding2.* unexpected and nothing missing.  get_loss_acc, load_model_from_ckpt and
-    _init_weights are the classifier's (the reference's class carries copies).  Forward only, evaluation mode only, no CPU
-    path: the encoder runs its levels on sa_eval_ops (PDAE_SA_EVAL=hip, the default; =layers: layer by layer)."""
+class _PointNetv2Classifier(Classifier):
+    """What PointNetv2_feat and PointNetv2 share: the config fields, the class count the loss kernels take, get_loss_acc's
+    label smoothing (the reference's get_loss_acc: eps 0.3 with smoothloss, else F.cross_entropy) and the trunk.  A
+    subclass builds pointnetv2_encoder."""
 
-    def __init__(self, config, **kwargs):
+    def __init__(self, config):
         super().__init__()
         self.config = config
         self.cls_dim = config.cls_dim
         self.smoothing = bool(config.get('smoothloss', False))
-        self.pointnetv2_encoder = PointNetv2_encoder(fused_eval=True)
+        if not 2 <= self.cls_dim <= 64:
+            raise NotImplementedError('%s: cls_dim = %d; the loss kernels take 2 to 64 classes'
+                                      % (type(self).__name__, self.cls_dim))
 
     @property
     def smooth_eps(self):
         return SMOOTH_EPS if self.smoothing else None
 
-    @torch.no_grad()
-    def forward(self, pts, capture=None):
-        """pts (B, N, 3+) -> the encoder's feature (B, 1024)."""
-        if self.training:
-            raise NotImplementedError('PointNetv2_feat: evaluation mode only -- the forward-only encoder of the linear-SVM '
-                                      'protocol; PointNet++ fine-tuning is not built')
-        if not pts.is_cuda:
-            raise RuntimeError('PointNetv2_feat: points must be on the GPU (there is no CPU path)')
-        begin_step(pts.device)
-        f = self.pointnetv2_encoder(pts[:, :, :3].contiguous(), capture)
+    def trunk(self, pts, capture):
+        """pts (B, N, 3) -> the encoder's feature (B, 1024) (PointCAE_pointnetv2.py:833-840)."""
+        f = self.pointnetv2_encoder(pts, capture)
         if capture is not None:
             capture.update(feature=f)
         return f
+
+
+@MODELS.register_module()
+class PointNetv2_feat(_PointNetv2Classifier):
+    """models/PointCAE_pointnetv2.py:936-1017: the PointNet++ encoder as the frozen feature extractor of
+    --svm_classification -- pointnetv2_encoder and nothing else that carries parameters, so a Point_CAE_PointNetv2
+    checkpoint loads with folding1.* / folding2.* unexpected and nothing missing.  get_loss_acc, load_model_from_ckpt and
+    _init_weights are the classifier's (the reference's class carries copies).  Forward only, evaluation mode only, no CPU
+    path: the encoder runs its levels on sa_eval_ops (PDAE_SA_EVAL=hip, the default; =layers: layer by layer)."""
+    eval_only = 'the forward-only encoder of the linear-SVM protocol; PointNet++ fine-tuning is not built'
+
+    def __init__(self, config, **kwargs):
+        super().__init__(config)
+        self.pointnetv2_encoder = PointNetv2_encoder(fused_eval=True)
+
+    forward = torch.no_grad()(Classifier.forward_features)       # pts (B, N, 3+) -> the encoder's feature (B, 1024)
 
 
 # measured on the graphed fine-tuning step at B = 32 (tools/bench_pointnetv2_cls.py, DESIGN.md section 7): split 3.84 ms against
@@ -297,7 +261,7 @@ SA_FIRST_DEFAULT = 'split'
 
 def sa_first_mode():
     """PDAE_SA_FIRST: how the classifier's sa1 and sa2 run their first layer in training mode -- 'split' (by source point,
-    sa_mlp.SplitFirstMLPMaxFunction) or 'grouped' (_GroupRows + sa_mlp.SharedMLPMaxFunction, the pretraining step's form:
+    sa_mlp.SplitFirstMLPMaxFunction) or 'grouped' (sa_mlp.group_rows + SharedMLPMaxFunction, the pretraining step's form:
     the fallback for the layouts the split kernels refuse, and the A/B and timing baseline)."""
     mode = os.environ.get('PDAE_SA_FIRST', '') or SA_FIRST_DEFAULT
     if mode not in ('split', 'grouped'):
@@ -306,7 +270,7 @@ def sa_first_mode():
 
 
 @MODELS.register_module()
-class PointNetv2(Classifier):
+class PointNetv2(_PointNetv2Classifier):
     """models/PointCAE_pointnetv2.py:749-842: the PointNet++ encoder of a Point_CAE_PointNetv2 checkpoint fine-tuned as a
     classifier.  pointnetv2_encoder is the auto-encoder's module under the same name, so its checkpoint loads with
     folding1.* / folding2.* unexpected and cls_head_finetune.* missing; the head Linear(1024, 512) -> BatchNorm1d -> ReLU ->
@@ -326,28 +290,10 @@ class PointNetv2(Classifier):
                             "differentiate training-mode BatchNorm only")
 
     def __init__(self, config, **kwargs):
-        super().__init__()
-        self.config = config
-        self.cls_dim = config.cls_dim
-        self.smoothing = bool(config.get('smoothloss', False))
-        if not 2 <= self.cls_dim <= 64:
-            raise NotImplementedError('PointNetv2: cls_dim = %d; the loss kernels take 2 to 64 classes' % self.cls_dim)
+        super().__init__(config)
         self.sa_first = sa_first_mode()
         self.pointnetv2_encoder = PointNetv2_encoder(fused_eval=True, split_first=self.sa_first == 'split')
         self.cls_head_finetune = nn.Sequential(
             nn.Linear(1024, 512), nn.BatchNorm1d(512), nn.ReLU(inplace=True), nn.Dropout(0.5),
             nn.Linear(512, 256), nn.BatchNorm1d(256), nn.ReLU(inplace=True), nn.Dropout(0.5),
             nn.Linear(256, self.cls_dim))
-
-    @property
-    def smooth_eps(self):
-        """get_loss_acc's label smoothing (the reference's PointNetv2.get_loss_acc): eps 0.3 with smoothloss, else
-        F.cross_entropy."""
-        return SMOOTH_EPS if self.smoothing else None
-
-    def trunk(self, pts, capture):
-        """pts (B, N, 3) -> the encoder's feature (B, 1024) (PointCAE_pointnetv2.py:833-840)."""
-        f = self.pointnetv2_encoder(pts, capture)
-        if capture is not None:
-            capture.update(feature=f)
-        return f

@@ -26,7 +26,6 @@ import torch
 import torch.nn as nn
 
 from . import _lib, nn_ops
-from .arena import begin_step
 from .classifier import Classifier
 from .point_cae_transformer import Block
 from .point_m2ae_group import Group, multi_scale_mask
@@ -239,6 +238,8 @@ class H_Encoder(nn.Module):
 class Point_M2AE_SVMFeature(Classifier):
     """Point_M2AE.py:1079-1169: the hierarchical encoder as the frozen feature extractor of --svm_classification.
     get_loss_acc, load_model_from_ckpt and _init_weights are the classifier's (the reference's class carries copies)."""
+    eval_only = ('the forward-only encoder of the linear-SVM protocol; training of Point-M2AE and Point_M2AE_Finetune are '
+                 'not built')
 
     def __init__(self, config, **kwargs):
         super().__init__()
@@ -267,16 +268,10 @@ class Point_M2AE_SVMFeature(Classifier):
             src = center
         return neighborhoods, centers, idxs
 
-    @torch.no_grad()
-    def forward(self, pts, capture=None):
-        """pts (B, N, 3+) -> the feature (B, encoder_dims[-1]) = mean + max over the last level's normed tokens."""
-        if self.training:
-            raise NotImplementedError('Point_M2AE_SVMFeature: evaluation mode only -- the forward-only encoder of the '
-                                      'linear-SVM protocol; training of Point-M2AE and Point_M2AE_Finetune are not built')
-        if not pts.is_cuda:
-            raise RuntimeError('Point_M2AE_SVMFeature: points must be on the GPU (there is no CPU path)')
-        begin_step(pts.device)
-        pts = pts[:, :, :3].contiguous()
+    forward = torch.no_grad()(Classifier.forward_features)
+
+    def trunk(self, pts, capture):
+        """pts (B, N, 3) -> the feature (B, encoder_dims[-1]) = mean + max over the last level's normed tokens."""
         neighborhoods, centers, idxs = self.group(pts)
         x = self.h_encoder(neighborhoods, centers, idxs, eval=True, capture=capture)
         f = nn_ops.max_plus_mean(x)

@@ -21,7 +21,6 @@ import torch
 import torch.nn as nn
 
 from . import finetune_ops, nn_ops
-from .arena import begin_step
 from .classifier import Classifier
 from .point_cae_transformer import Encoder, Group, TransformerEncoder, pos_embed_layers, trunc_normal_
 from .registry import MODELS
@@ -117,6 +116,8 @@ class PointTransformerNoClassTokenSVMFeature(Classifier):
     and _init_weights are the classifier's (the reference's class carries copies).  Never trained: forward only,
     evaluation mode only, no CPU path."""
     late_grad_prefixes = ()
+    eval_only = ('the frozen feature extractor of the linear-SVM protocol; PointTransformerNoClassToken fine-tuning is '
+                 'not built')
 
     def __init__(self, config, **kwargs):
         super().__init__()
@@ -142,17 +143,10 @@ class PointTransformerNoClassTokenSVMFeature(Classifier):
         self.blocks = TransformerEncoder(self.trans_dim, self.depth, self.num_heads, dpr)
         self.norm = nn.LayerNorm(self.trans_dim)
 
-    @torch.no_grad()
-    def forward(self, pts, capture=None):
-        """pts (B, N, 3+) -> the feature (B, trans_dim)."""
-        if self.training:
-            raise NotImplementedError('PointTransformerNoClassTokenSVMFeature: evaluation mode only -- the frozen feature '
-                                      'extractor of the linear-SVM protocol; PointTransformerNoClassToken fine-tuning is '
-                                      'not built')
-        if not pts.is_cuda:
-            raise RuntimeError('PointTransformerNoClassTokenSVMFeature: points must be on the GPU (there is no CPU path)')
-        pts = pts[:, :, :3].contiguous()
-        begin_step(pts.device)
+    forward = torch.no_grad()(Classifier.forward_features)
+
+    def trunk(self, pts, capture):
+        """pts (B, N, 3) -> the feature (B, trans_dim)."""
         B, G, C = pts.shape[0], self.num_group, self.trans_dim
         neighborhood, center = self.group_divider(pts, capture)      # (capture also receives fps_idx, knn_idx)
         tokens = self.encoder(neighborhood)                                           # (B, G, C)

@@ -9,17 +9,15 @@ estimates, as models/PointCAE_pointnetv2.py:936-1017 (PointNetv2_feat) runs it u
 In evaluation mode the first layer is linear per source point up to the centred coordinates, so its feature columns
 run once per source point -- P = features W0f^T on the row GEMM, (B*N, C1) rows instead of (B*np*ns, C1) -- and
 pdae_sa_eval_forward does the rest of the level in one launch: no (B*np*ns, .) tensor exists.  The group-all level has
-128 rows per cloud and needs no new kernel: pdae_conv_stats per layer with the running-estimate scale / shift as the
-next layer's prologue (its batch statistics are computed and ignored), then pdae_bnrelu_group_max.
+128 rows per cloud and needs no new kernel: the forward of the training chain (sa_mlp.mlp_max_forward) with the
+running-estimate scale / shift as the next layer's prologue (each layer's batch statistics are computed and ignored).
 
 PDAE_SA_EVAL=hip (default) | layers: `layers` keeps the layer-by-layer form of PointnetSAModule.forward (the fallback for
 layouts the kernel refuses, and the timing baseline of tools/bench_sa_eval.py).
 """
 import os
 
-import torch
-
-from . import _lib
+from . import _lib, sa_mlp
 from .rows import bn_eval_affine, empty, insert_zero_col, rows_gemm
 
 MODES = ('hip', 'layers')
@@ -78,22 +76,12 @@ def level(xyz, new_xyz, idx, features, layers):
 
 def group_all(xyz, features, layers):
     """The group-all level in evaluation mode: xyz (B,N,3), features (B*N, C) rows -> (B, C_last).  None when N > 256
-    or C is not a multiple of 4 (pdae_bnrelu_group_max, the row GEMMs)."""
+    or C is not a multiple of 4 (the pooling kernel, the row GEMMs)."""
     B, N, _ = xyz.shape
     if N > 256 or features is None or features.shape[1] % 4 != 0:
         return None
-    g = xyz.reshape(B * N, 3)
-    x = torch.cat([g, g.new_zeros(B * N, 1), features], dim=1)                  # [xyz | 0 | features], K a multiple of 4
-    sc = sh = None
-    for i, (w, scale, shift) in enumerate(layer_affines(layers)):
-        w = (insert_zero_col(w, 3) if i == 0 else w).contiguous()
-        y = empty((B * N, w.shape[0]), x)
-        stats = empty((8, 2, w.shape[0]), x)                                    # (this layer's batch statistics: unused)
-        _lib.call('pdae_conv_stats', x, B * N, w.shape[0], w.shape[1], _lib.ptr(x), _lib.ptr(sc), _lib.ptr(sh),
-                  _lib.ptr(w), _lib.ptr(y), _lib.ptr(stats))
-        x, sc, sh = y, scale, shift
-    out = empty((B, x.shape[1]), x)
-    arg = empty((B, x.shape[1]), x, torch.uint8)
-    _lib.call('pdae_bnrelu_group_max', x, B, N, x.shape[1], _lib.ptr(x), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(out),
-              _lib.ptr(arg))
-    return out
+    x = sa_mlp.all_rows(xyz.reshape(B * N, 3), features)                        # [xyz | 0 | features], K a multiple of 4
+    affines = layer_affines(layers)
+    ws = [(insert_zero_col(w, 3) if i == 0 else w).contiguous() for i, (w, _, _) in enumerate(affines)]
+    # (each layer's batch statistics are computed and ignored; the winners reach no backward, so ARG_HOOK is not asked)
+    return sa_mlp.mlp_max_forward(x, None, None, ws, lambda i, stats: affines[i][1:], N, hook=False)[0]

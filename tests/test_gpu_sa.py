@@ -37,17 +37,27 @@ def _reference(x64, mlp64, groups, ns):
 
 
 @pytest.mark.parametrize('groups,ns,spec', [(512, 32, [4, 64, 64, 128]), (96, 64, [132, 128, 128, 256]),
-                                            (3, 128, [260, 256, 512, 1024]), (40, 16, [8, 32, 64])])
+                                            (3, 128, [260, 256, 512, 1024]), (40, 16, [8, 32, 64]),
+                                            (40, 16, [8, 32, 96])])
 def test_shared_mlp_max_matches_torch_fp64(groups, ns, spec):
-    from point_dae_amd import sa_mlp
+    """The last case has a last width whose quarter, 24, does not divide 256: the max-pool gradient takes the dense form
+    (group_max_scatter_n + bnrelu_backward) inside the Function, the others go straight through the pool."""
+    from point_dae_amd import _lib, sa_mlp
     mlp = _level(spec, groups)
     mlp64 = copy.deepcopy(mlp).double()
     g = torch.Generator(device='cuda').manual_seed(ns)
     x = torch.randn(groups * ns, spec[0], device='cuda', generator=g).requires_grad_()
     x64 = x.detach().double().requires_grad_()
     go = torch.randn(groups, spec[-1], device='cuda', generator=g)
-    out = sa_mlp.shared_mlp_max(x, list(mlp), ns)
-    out.backward(go)
+    calls = []
+    _lib.CALL_HOOK = lambda name, args: calls.append(name)
+    try:
+        out = sa_mlp.shared_mlp_max(x, list(mlp), ns)
+        out.backward(go)
+    finally:
+        _lib.CALL_HOOK = None
+    dense = 256 % (spec[-1] // 4) != 0
+    assert ('pdae_group_max_scatter_n' in calls) == dense and ('pdae_pool_bn_backward' in calls) == (not dense)
     ref = _reference(x64, mlp64, groups, ns)
     ref.backward(go.double())
     _close(out, ref, 2e-5)

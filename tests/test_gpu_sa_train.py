@@ -261,6 +261,64 @@ def test_level_split_against_grouped_on_the_same_winners(i):
             assert _rel(q, p) <= 1e-5, (n, _rel(q, p))
 
 
+# The forms of the training-mode level that the cases above do not reach: (B, N, npoint, nsample, C, radius), npoint None for
+# the group-all level, and whether the shared MLP runs as the fused chain (sa_mlp) or layer by layer (_ConvBN.rows).
+FORMS = {'framework_grouping': ((1, 4128, 8, 32, 4, 0.3), True),      # N > 4096: index_select / cat, then the fused chain
+         'rows_not_32': ((1, 64, 3, 8, 4, 0.45), False),              # 24 rows: the grouping kernel, then layer by layer
+         'group_all': ((2, 128, None, None, 4, None), True),
+         'group_all_wide': ((2, 300, None, None, 4, None), False)}    # more than 256 rows per group: layer by layer
+
+
+@pytest.mark.parametrize('form', list(FORMS))
+def test_level_forms_against_fp64_on_the_captured_grouping(form):
+    """PointnetSAModule in training mode, widths [C, 16, 32], on the forms of its dispatcher that no other test runs:
+    output (2e-5), every parameter gradient and the feature gradient (2e-4) against the fp64 layer stack of
+    tests/test_gpu_sa.py applied to the fp64 grouped tensor built from the captured FPS / ball-query indices; which form
+    ran is read from the list of library calls.  No winners are injected and no element is excluded."""
+    import copy
+    from test_gpu_sa import _reference
+    from point_dae_amd.point_cae_pointnetv2 import PointnetSAModule
+    from point_dae_amd.synthetic import shapenet_like_clouds
+    (B, N, npoint, ns, C, radius), chain = FORMS[form]
+    torch.manual_seed(11)
+    m = PointnetSAModule(mlp=[C, 16, 32], npoint=npoint, radius=radius, nsample=ns).cuda().train()
+    with torch.no_grad():
+        for layer in m.mlps[0]:
+            layer.bn.bn.weight.uniform_(0.5, 1.5)
+            layer.bn.bn.bias.uniform_(-0.3, 0.3)
+    mlp64 = copy.deepcopy(m.mlps[0]).double()
+    g = torch.Generator().manual_seed(5)
+    xyz = torch.from_numpy(shapenet_like_clouds(B, N, seed=60)).cuda()
+    c = dict(xyz=xyz, feats=torch.randn(B * N, C, generator=g).cuda())
+    groups, per = (B, N) if npoint is None else (B * npoint, ns)
+    dout = torch.randn(groups, 32, generator=g).cuda()
+    out, grads, calls, cap = _run_level(m, c, None, dout)
+
+    assert ('pdae_conv_stats' in calls) == chain and ('pdae_bnrelu_group_max' in calls) == chain
+    assert ('pdae_sa_group_rows' in calls) == (form == 'rows_not_32')
+    assert 'pdae_sa_first_forward' not in calls and 'first' not in cap
+
+    f64 = c['feats'].double().requires_grad_()
+    p64 = xyz.double().reshape(B * N, 3)
+    if npoint is None:
+        rows = torch.cat([p64, f64], dim=1)
+    else:
+        base = torch.arange(B, device='cuda') * N
+        src = (cap['ball_idx'].long() + base.view(B, 1, 1)).reshape(-1)
+        centres = p64[(cap['fps_idx'].long() + base.view(B, 1)).reshape(-1)].reshape(B, npoint, 1, 3)
+        rows = torch.cat([(p64[src].reshape(B, npoint, ns, 3) - centres).reshape(-1, 3), f64[src]], dim=1)
+    ref = _reference(rows, mlp64, groups, per)
+    ref.backward(dout.double())
+    want = {n: q.grad.reshape(grads[n].shape) for (n, _), q in zip(m.named_parameters(), mlp64.parameters())}
+    want['features'] = f64.grad
+    assert set(want) == set(grads)
+    figures = [('output', _rel(out, ref), 2e-5)] + [('d ' + n, _rel(grads[n], want[n]), 2e-4) for n in want]
+    for name, e, _ in figures:
+        print('%s: %-34s %.3e' % (form, name, e))
+    for name, e, bar in figures:
+        assert e <= bar, (form, name, e)
+
+
 def test_a_refused_layout_is_answered_before_a_pointer_is_read_and_runs_grouped():
     from point_dae_amd import _lib, sa_mlp
     h = _lib.lib()

@@ -124,6 +124,266 @@ def test_forward_refuses_the_cpu_and_training_mode(name):
         model.train()(pts)
 
 
+# The four frozen feature extractors: config, the tail of the training-mode refusal (None: the model has none), and the
+# state_dict keys in order, recorded before the classes were put on Classifier.forward_features.
+FEATURE_MODELS = {
+    'PointNetv2_feat': ('cfgs/finetune_modelnet_svm_pointnetv2.yaml',
+                        'the forward-only encoder of the linear-SVM protocol; PointNet++ fine-tuning is not built'),
+    'DGCNN_feat': ('cfgs/finetune_modelnet_svm_dgcnn.yaml', None),
+    'PointTransformerNoClassTokenSVMFeature': (
+        'cfgs/finetune_modelnet_svm_transformer.yaml',
+        'the frozen feature extractor of the linear-SVM protocol; PointTransformerNoClassToken fine-tuning is not built'),
+    'Point_M2AE_SVMFeature': (
+        'cfgs/finetune_modelnet_svm_pointm2ae.yaml',
+        'the forward-only encoder of the linear-SVM protocol; training of Point-M2AE and Point_M2AE_Finetune are not built'),
+}
+FEATURE_KEYS = {
+    'PointNetv2_feat': """
+        pointnetv2_encoder.sa1.mlps.0.layer0.conv.weight pointnetv2_encoder.sa1.mlps.0.layer0.bn.bn.weight
+        pointnetv2_encoder.sa1.mlps.0.layer0.bn.bn.bias pointnetv2_encoder.sa1.mlps.0.layer0.bn.bn.running_mean
+        pointnetv2_encoder.sa1.mlps.0.layer0.bn.bn.running_var
+        pointnetv2_encoder.sa1.mlps.0.layer0.bn.bn.num_batches_tracked pointnetv2_encoder.sa1.mlps.0.layer1.conv.weight
+        pointnetv2_encoder.sa1.mlps.0.layer1.bn.bn.weight pointnetv2_encoder.sa1.mlps.0.layer1.bn.bn.bias
+        pointnetv2_encoder.sa1.mlps.0.layer1.bn.bn.running_mean pointnetv2_encoder.sa1.mlps.0.layer1.bn.bn.running_var
+        pointnetv2_encoder.sa1.mlps.0.layer1.bn.bn.num_batches_tracked pointnetv2_encoder.sa1.mlps.0.layer2.conv.weight
+        pointnetv2_encoder.sa1.mlps.0.layer2.bn.bn.weight pointnetv2_encoder.sa1.mlps.0.layer2.bn.bn.bias
+        pointnetv2_encoder.sa1.mlps.0.layer2.bn.bn.running_mean pointnetv2_encoder.sa1.mlps.0.layer2.bn.bn.running_var
+        pointnetv2_encoder.sa1.mlps.0.layer2.bn.bn.num_batches_tracked pointnetv2_encoder.sa2.mlps.0.layer0.conv.weight
+        pointnetv2_encoder.sa2.mlps.0.layer0.bn.bn.weight pointnetv2_encoder.sa2.mlps.0.layer0.bn.bn.bias
+        pointnetv2_encoder.sa2.mlps.0.layer0.bn.bn.running_mean pointnetv2_encoder.sa2.mlps.0.layer0.bn.bn.running_var
+        pointnetv2_encoder.sa2.mlps.0.layer0.bn.bn.num_batches_tracked pointnetv2_encoder.sa2.mlps.0.layer1.conv.weight
+        pointnetv2_encoder.sa2.mlps.0.layer1.bn.bn.weight pointnetv2_encoder.sa2.mlps.0.layer1.bn.bn.bias
+        pointnetv2_encoder.sa2.mlps.0.layer1.bn.bn.running_mean pointnetv2_encoder.sa2.mlps.0.layer1.bn.bn.running_var
+        pointnetv2_encoder.sa2.mlps.0.layer1.bn.bn.num_batches_tracked pointnetv2_encoder.sa2.mlps.0.layer2.conv.weight
+        pointnetv2_encoder.sa2.mlps.0.layer2.bn.bn.weight pointnetv2_encoder.sa2.mlps.0.layer2.bn.bn.bias
+        pointnetv2_encoder.sa2.mlps.0.layer2.bn.bn.running_mean pointnetv2_encoder.sa2.mlps.0.layer2.bn.bn.running_var
+        pointnetv2_encoder.sa2.mlps.0.layer2.bn.bn.num_batches_tracked pointnetv2_encoder.sa3.mlps.0.layer0.conv.weight
+        pointnetv2_encoder.sa3.mlps.0.layer0.bn.bn.weight pointnetv2_encoder.sa3.mlps.0.layer0.bn.bn.bias
+        pointnetv2_encoder.sa3.mlps.0.layer0.bn.bn.running_mean pointnetv2_encoder.sa3.mlps.0.layer0.bn.bn.running_var
+        pointnetv2_encoder.sa3.mlps.0.layer0.bn.bn.num_batches_tracked pointnetv2_encoder.sa3.mlps.0.layer1.conv.weight
+        pointnetv2_encoder.sa3.mlps.0.layer1.bn.bn.weight pointnetv2_encoder.sa3.mlps.0.layer1.bn.bn.bias
+        pointnetv2_encoder.sa3.mlps.0.layer1.bn.bn.running_mean pointnetv2_encoder.sa3.mlps.0.layer1.bn.bn.running_var
+        pointnetv2_encoder.sa3.mlps.0.layer1.bn.bn.num_batches_tracked pointnetv2_encoder.sa3.mlps.0.layer2.conv.weight
+        pointnetv2_encoder.sa3.mlps.0.layer2.bn.bn.weight pointnetv2_encoder.sa3.mlps.0.layer2.bn.bn.bias
+        pointnetv2_encoder.sa3.mlps.0.layer2.bn.bn.running_mean pointnetv2_encoder.sa3.mlps.0.layer2.bn.bn.running_var
+        pointnetv2_encoder.sa3.mlps.0.layer2.bn.bn.num_batches_tracked
+        """,
+    'DGCNN_feat': """
+        dgcnn_encoder.bn1.weight dgcnn_encoder.bn1.bias dgcnn_encoder.bn1.running_mean dgcnn_encoder.bn1.running_var
+        dgcnn_encoder.bn1.num_batches_tracked dgcnn_encoder.bn2.weight dgcnn_encoder.bn2.bias
+        dgcnn_encoder.bn2.running_mean dgcnn_encoder.bn2.running_var dgcnn_encoder.bn2.num_batches_tracked
+        dgcnn_encoder.bn3.weight dgcnn_encoder.bn3.bias dgcnn_encoder.bn3.running_mean dgcnn_encoder.bn3.running_var
+        dgcnn_encoder.bn3.num_batches_tracked dgcnn_encoder.bn4.weight dgcnn_encoder.bn4.bias
+        dgcnn_encoder.bn4.running_mean dgcnn_encoder.bn4.running_var dgcnn_encoder.bn4.num_batches_tracked
+        dgcnn_encoder.bn5.weight dgcnn_encoder.bn5.bias dgcnn_encoder.bn5.running_mean dgcnn_encoder.bn5.running_var
+        dgcnn_encoder.bn5.num_batches_tracked dgcnn_encoder.conv1.0.weight dgcnn_encoder.conv1.1.weight
+        dgcnn_encoder.conv1.1.bias dgcnn_encoder.conv1.1.running_mean dgcnn_encoder.conv1.1.running_var
+        dgcnn_encoder.conv1.1.num_batches_tracked dgcnn_encoder.conv2.0.weight dgcnn_encoder.conv2.1.weight
+        dgcnn_encoder.conv2.1.bias dgcnn_encoder.conv2.1.running_mean dgcnn_encoder.conv2.1.running_var
+        dgcnn_encoder.conv2.1.num_batches_tracked dgcnn_encoder.conv3.0.weight dgcnn_encoder.conv3.1.weight
+        dgcnn_encoder.conv3.1.bias dgcnn_encoder.conv3.1.running_mean dgcnn_encoder.conv3.1.running_var
+        dgcnn_encoder.conv3.1.num_batches_tracked dgcnn_encoder.conv4.0.weight dgcnn_encoder.conv4.1.weight
+        dgcnn_encoder.conv4.1.bias dgcnn_encoder.conv4.1.running_mean dgcnn_encoder.conv4.1.running_var
+        dgcnn_encoder.conv4.1.num_batches_tracked dgcnn_encoder.conv5.0.weight dgcnn_encoder.conv5.1.weight
+        dgcnn_encoder.conv5.1.bias dgcnn_encoder.conv5.1.running_mean dgcnn_encoder.conv5.1.running_var
+        dgcnn_encoder.conv5.1.num_batches_tracked
+        """,
+    'PointTransformerNoClassTokenSVMFeature': """
+        encoder.first_conv.0.weight encoder.first_conv.0.bias encoder.first_conv.1.weight encoder.first_conv.1.bias
+        encoder.first_conv.1.running_mean encoder.first_conv.1.running_var encoder.first_conv.1.num_batches_tracked
+        encoder.first_conv.3.weight encoder.first_conv.3.bias encoder.second_conv.0.weight encoder.second_conv.0.bias
+        encoder.second_conv.1.weight encoder.second_conv.1.bias encoder.second_conv.1.running_mean
+        encoder.second_conv.1.running_var encoder.second_conv.1.num_batches_tracked encoder.second_conv.3.weight
+        encoder.second_conv.3.bias pos_embed.0.weight pos_embed.0.bias pos_embed.2.weight pos_embed.2.bias
+        blocks.blocks.0.norm1.weight blocks.blocks.0.norm1.bias blocks.blocks.0.norm2.weight blocks.blocks.0.norm2.bias
+        blocks.blocks.0.mlp.fc1.weight blocks.blocks.0.mlp.fc1.bias blocks.blocks.0.mlp.fc2.weight
+        blocks.blocks.0.mlp.fc2.bias blocks.blocks.0.attn.qkv.weight blocks.blocks.0.attn.proj.weight
+        blocks.blocks.0.attn.proj.bias blocks.blocks.1.norm1.weight blocks.blocks.1.norm1.bias
+        blocks.blocks.1.norm2.weight blocks.blocks.1.norm2.bias blocks.blocks.1.mlp.fc1.weight
+        blocks.blocks.1.mlp.fc1.bias blocks.blocks.1.mlp.fc2.weight blocks.blocks.1.mlp.fc2.bias
+        blocks.blocks.1.attn.qkv.weight blocks.blocks.1.attn.proj.weight blocks.blocks.1.attn.proj.bias
+        blocks.blocks.2.norm1.weight blocks.blocks.2.norm1.bias blocks.blocks.2.norm2.weight blocks.blocks.2.norm2.bias
+        blocks.blocks.2.mlp.fc1.weight blocks.blocks.2.mlp.fc1.bias blocks.blocks.2.mlp.fc2.weight
+        blocks.blocks.2.mlp.fc2.bias blocks.blocks.2.attn.qkv.weight blocks.blocks.2.attn.proj.weight
+        blocks.blocks.2.attn.proj.bias blocks.blocks.3.norm1.weight blocks.blocks.3.norm1.bias
+        blocks.blocks.3.norm2.weight blocks.blocks.3.norm2.bias blocks.blocks.3.mlp.fc1.weight
+        blocks.blocks.3.mlp.fc1.bias blocks.blocks.3.mlp.fc2.weight blocks.blocks.3.mlp.fc2.bias
+        blocks.blocks.3.attn.qkv.weight blocks.blocks.3.attn.proj.weight blocks.blocks.3.attn.proj.bias
+        blocks.blocks.4.norm1.weight blocks.blocks.4.norm1.bias blocks.blocks.4.norm2.weight blocks.blocks.4.norm2.bias
+        blocks.blocks.4.mlp.fc1.weight blocks.blocks.4.mlp.fc1.bias blocks.blocks.4.mlp.fc2.weight
+        blocks.blocks.4.mlp.fc2.bias blocks.blocks.4.attn.qkv.weight blocks.blocks.4.attn.proj.weight
+        blocks.blocks.4.attn.proj.bias blocks.blocks.5.norm1.weight blocks.blocks.5.norm1.bias
+        blocks.blocks.5.norm2.weight blocks.blocks.5.norm2.bias blocks.blocks.5.mlp.fc1.weight
+        blocks.blocks.5.mlp.fc1.bias blocks.blocks.5.mlp.fc2.weight blocks.blocks.5.mlp.fc2.bias
+        blocks.blocks.5.attn.qkv.weight blocks.blocks.5.attn.proj.weight blocks.blocks.5.attn.proj.bias
+        blocks.blocks.6.norm1.weight blocks.blocks.6.norm1.bias blocks.blocks.6.norm2.weight blocks.blocks.6.norm2.bias
+        blocks.blocks.6.mlp.fc1.weight blocks.blocks.6.mlp.fc1.bias blocks.blocks.6.mlp.fc2.weight
+        blocks.blocks.6.mlp.fc2.bias blocks.blocks.6.attn.qkv.weight blocks.blocks.6.attn.proj.weight
+        blocks.blocks.6.attn.proj.bias blocks.blocks.7.norm1.weight blocks.blocks.7.norm1.bias
+        blocks.blocks.7.norm2.weight blocks.blocks.7.norm2.bias blocks.blocks.7.mlp.fc1.weight
+        blocks.blocks.7.mlp.fc1.bias blocks.blocks.7.mlp.fc2.weight blocks.blocks.7.mlp.fc2.bias
+        blocks.blocks.7.attn.qkv.weight blocks.blocks.7.attn.proj.weight blocks.blocks.7.attn.proj.bias
+        blocks.blocks.8.norm1.weight blocks.blocks.8.norm1.bias blocks.blocks.8.norm2.weight blocks.blocks.8.norm2.bias
+        blocks.blocks.8.mlp.fc1.weight blocks.blocks.8.mlp.fc1.bias blocks.blocks.8.mlp.fc2.weight
+        blocks.blocks.8.mlp.fc2.bias blocks.blocks.8.attn.qkv.weight blocks.blocks.8.attn.proj.weight
+        blocks.blocks.8.attn.proj.bias blocks.blocks.9.norm1.weight blocks.blocks.9.norm1.bias
+        blocks.blocks.9.norm2.weight blocks.blocks.9.norm2.bias blocks.blocks.9.mlp.fc1.weight
+        blocks.blocks.9.mlp.fc1.bias blocks.blocks.9.mlp.fc2.weight blocks.blocks.9.mlp.fc2.bias
+        blocks.blocks.9.attn.qkv.weight blocks.blocks.9.attn.proj.weight blocks.blocks.9.attn.proj.bias
+        blocks.blocks.10.norm1.weight blocks.blocks.10.norm1.bias blocks.blocks.10.norm2.weight
+        blocks.blocks.10.norm2.bias blocks.blocks.10.mlp.fc1.weight blocks.blocks.10.mlp.fc1.bias
+        blocks.blocks.10.mlp.fc2.weight blocks.blocks.10.mlp.fc2.bias blocks.blocks.10.attn.qkv.weight
+        blocks.blocks.10.attn.proj.weight blocks.blocks.10.attn.proj.bias blocks.blocks.11.norm1.weight
+        blocks.blocks.11.norm1.bias blocks.blocks.11.norm2.weight blocks.blocks.11.norm2.bias
+        blocks.blocks.11.mlp.fc1.weight blocks.blocks.11.mlp.fc1.bias blocks.blocks.11.mlp.fc2.weight
+        blocks.blocks.11.mlp.fc2.bias blocks.blocks.11.attn.qkv.weight blocks.blocks.11.attn.proj.weight
+        blocks.blocks.11.attn.proj.bias norm.weight norm.bias
+        """,
+    'Point_M2AE_SVMFeature': """
+        h_encoder.token_embed.0.first_conv.0.weight h_encoder.token_embed.0.first_conv.0.bias
+        h_encoder.token_embed.0.first_conv.1.weight h_encoder.token_embed.0.first_conv.1.bias
+        h_encoder.token_embed.0.first_conv.1.running_mean h_encoder.token_embed.0.first_conv.1.running_var
+        h_encoder.token_embed.0.first_conv.1.num_batches_tracked h_encoder.token_embed.0.first_conv.3.weight
+        h_encoder.token_embed.0.first_conv.3.bias h_encoder.token_embed.0.second_conv.0.weight
+        h_encoder.token_embed.0.second_conv.0.bias h_encoder.token_embed.0.second_conv.1.weight
+        h_encoder.token_embed.0.second_conv.1.bias h_encoder.token_embed.0.second_conv.1.running_mean
+        h_encoder.token_embed.0.second_conv.1.running_var h_encoder.token_embed.0.second_conv.1.num_batches_tracked
+        h_encoder.token_embed.0.second_conv.3.weight h_encoder.token_embed.0.second_conv.3.bias
+        h_encoder.token_embed.1.first_conv.0.weight h_encoder.token_embed.1.first_conv.0.bias
+        h_encoder.token_embed.1.first_conv.1.weight h_encoder.token_embed.1.first_conv.1.bias
+        h_encoder.token_embed.1.first_conv.1.running_mean h_encoder.token_embed.1.first_conv.1.running_var
+        h_encoder.token_embed.1.first_conv.1.num_batches_tracked h_encoder.token_embed.1.first_conv.3.weight
+        h_encoder.token_embed.1.first_conv.3.bias h_encoder.token_embed.1.second_conv.0.weight
+        h_encoder.token_embed.1.second_conv.0.bias h_encoder.token_embed.1.second_conv.1.weight
+        h_encoder.token_embed.1.second_conv.1.bias h_encoder.token_embed.1.second_conv.1.running_mean
+        h_encoder.token_embed.1.second_conv.1.running_var h_encoder.token_embed.1.second_conv.1.num_batches_tracked
+        h_encoder.token_embed.1.second_conv.3.weight h_encoder.token_embed.1.second_conv.3.bias
+        h_encoder.token_embed.2.first_conv.0.weight h_encoder.token_embed.2.first_conv.0.bias
+        h_encoder.token_embed.2.first_conv.1.weight h_encoder.token_embed.2.first_conv.1.bias
+        h_encoder.token_embed.2.first_conv.1.running_mean h_encoder.token_embed.2.first_conv.1.running_var
+        h_encoder.token_embed.2.first_conv.1.num_batches_tracked h_encoder.token_embed.2.first_conv.3.weight
+        h_encoder.token_embed.2.first_conv.3.bias h_encoder.token_embed.2.second_conv.0.weight
+        h_encoder.token_embed.2.second_conv.0.bias h_encoder.token_embed.2.second_conv.1.weight
+        h_encoder.token_embed.2.second_conv.1.bias h_encoder.token_embed.2.second_conv.1.running_mean
+        h_encoder.token_embed.2.second_conv.1.running_var h_encoder.token_embed.2.second_conv.1.num_batches_tracked
+        h_encoder.token_embed.2.second_conv.3.weight h_encoder.token_embed.2.second_conv.3.bias
+        h_encoder.encoder_pos_embeds.0.0.weight h_encoder.encoder_pos_embeds.0.0.bias
+        h_encoder.encoder_pos_embeds.0.2.weight h_encoder.encoder_pos_embeds.0.2.bias
+        h_encoder.encoder_pos_embeds.1.0.weight h_encoder.encoder_pos_embeds.1.0.bias
+        h_encoder.encoder_pos_embeds.1.2.weight h_encoder.encoder_pos_embeds.1.2.bias
+        h_encoder.encoder_pos_embeds.2.0.weight h_encoder.encoder_pos_embeds.2.0.bias
+        h_encoder.encoder_pos_embeds.2.2.weight h_encoder.encoder_pos_embeds.2.2.bias
+        h_encoder.encoder_blocks.0.blocks.0.norm1.weight h_encoder.encoder_blocks.0.blocks.0.norm1.bias
+        h_encoder.encoder_blocks.0.blocks.0.norm2.weight h_encoder.encoder_blocks.0.blocks.0.norm2.bias
+        h_encoder.encoder_blocks.0.blocks.0.mlp.fc1.weight h_encoder.encoder_blocks.0.blocks.0.mlp.fc1.bias
+        h_encoder.encoder_blocks.0.blocks.0.mlp.fc2.weight h_encoder.encoder_blocks.0.blocks.0.mlp.fc2.bias
+        h_encoder.encoder_blocks.0.blocks.0.attn.qkv.weight h_encoder.encoder_blocks.0.blocks.0.attn.proj.weight
+        h_encoder.encoder_blocks.0.blocks.0.attn.proj.bias h_encoder.encoder_blocks.0.blocks.1.norm1.weight
+        h_encoder.encoder_blocks.0.blocks.1.norm1.bias h_encoder.encoder_blocks.0.blocks.1.norm2.weight
+        h_encoder.encoder_blocks.0.blocks.1.norm2.bias h_encoder.encoder_blocks.0.blocks.1.mlp.fc1.weight
+        h_encoder.encoder_blocks.0.blocks.1.mlp.fc1.bias h_encoder.encoder_blocks.0.blocks.1.mlp.fc2.weight
+        h_encoder.encoder_blocks.0.blocks.1.mlp.fc2.bias h_encoder.encoder_blocks.0.blocks.1.attn.qkv.weight
+        h_encoder.encoder_blocks.0.blocks.1.attn.proj.weight h_encoder.encoder_blocks.0.blocks.1.attn.proj.bias
+        h_encoder.encoder_blocks.0.blocks.2.norm1.weight h_encoder.encoder_blocks.0.blocks.2.norm1.bias
+        h_encoder.encoder_blocks.0.blocks.2.norm2.weight h_encoder.encoder_blocks.0.blocks.2.norm2.bias
+        h_encoder.encoder_blocks.0.blocks.2.mlp.fc1.weight h_encoder.encoder_blocks.0.blocks.2.mlp.fc1.bias
+        h_encoder.encoder_blocks.0.blocks.2.mlp.fc2.weight h_encoder.encoder_blocks.0.blocks.2.mlp.fc2.bias
+        h_encoder.encoder_blocks.0.blocks.2.attn.qkv.weight h_encoder.encoder_blocks.0.blocks.2.attn.proj.weight
+        h_encoder.encoder_blocks.0.blocks.2.attn.proj.bias h_encoder.encoder_blocks.0.blocks.3.norm1.weight
+        h_encoder.encoder_blocks.0.blocks.3.norm1.bias h_encoder.encoder_blocks.0.blocks.3.norm2.weight
+        h_encoder.encoder_blocks.0.blocks.3.norm2.bias h_encoder.encoder_blocks.0.blocks.3.mlp.fc1.weight
+        h_encoder.encoder_blocks.0.blocks.3.mlp.fc1.bias h_encoder.encoder_blocks.0.blocks.3.mlp.fc2.weight
+        h_encoder.encoder_blocks.0.blocks.3.mlp.fc2.bias h_encoder.encoder_blocks.0.blocks.3.attn.qkv.weight
+        h_encoder.encoder_blocks.0.blocks.3.attn.proj.weight h_encoder.encoder_blocks.0.blocks.3.attn.proj.bias
+        h_encoder.encoder_blocks.0.blocks.4.norm1.weight h_encoder.encoder_blocks.0.blocks.4.norm1.bias
+        h_encoder.encoder_blocks.0.blocks.4.norm2.weight h_encoder.encoder_blocks.0.blocks.4.norm2.bias
+        h_encoder.encoder_blocks.0.blocks.4.mlp.fc1.weight h_encoder.encoder_blocks.0.blocks.4.mlp.fc1.bias
+        h_encoder.encoder_blocks.0.blocks.4.mlp.fc2.weight h_encoder.encoder_blocks.0.blocks.4.mlp.fc2.bias
+        h_encoder.encoder_blocks.0.blocks.4.attn.qkv.weight h_encoder.encoder_blocks.0.blocks.4.attn.proj.weight
+        h_encoder.encoder_blocks.0.blocks.4.attn.proj.bias h_encoder.encoder_blocks.1.blocks.0.norm1.weight
+        h_encoder.encoder_blocks.1.blocks.0.norm1.bias h_encoder.encoder_blocks.1.blocks.0.norm2.weight
+        h_encoder.encoder_blocks.1.blocks.0.norm2.bias h_encoder.encoder_blocks.1.blocks.0.mlp.fc1.weight
+        h_encoder.encoder_blocks.1.blocks.0.mlp.fc1.bias h_encoder.encoder_blocks.1.blocks.0.mlp.fc2.weight
+        h_encoder.encoder_blocks.1.blocks.0.mlp.fc2.bias h_encoder.encoder_blocks.1.blocks.0.attn.qkv.weight
+        h_encoder.encoder_blocks.1.blocks.0.attn.proj.weight h_encoder.encoder_blocks.1.blocks.0.attn.proj.bias
+        h_encoder.encoder_blocks.1.blocks.1.norm1.weight h_encoder.encoder_blocks.1.blocks.1.norm1.bias
+        h_encoder.encoder_blocks.1.blocks.1.norm2.weight h_encoder.encoder_blocks.1.blocks.1.norm2.bias
+        h_encoder.encoder_blocks.1.blocks.1.mlp.fc1.weight h_encoder.encoder_blocks.1.blocks.1.mlp.fc1.bias
+        h_encoder.encoder_blocks.1.blocks.1.mlp.fc2.weight h_encoder.encoder_blocks.1.blocks.1.mlp.fc2.bias
+        h_encoder.encoder_blocks.1.blocks.1.attn.qkv.weight h_encoder.encoder_blocks.1.blocks.1.attn.proj.weight
+        h_encoder.encoder_blocks.1.blocks.1.attn.proj.bias h_encoder.encoder_blocks.1.blocks.2.norm1.weight
+        h_encoder.encoder_blocks.1.blocks.2.norm1.bias h_encoder.encoder_blocks.1.blocks.2.norm2.weight
+        h_encoder.encoder_blocks.1.blocks.2.norm2.bias h_encoder.encoder_blocks.1.blocks.2.mlp.fc1.weight
+        h_encoder.encoder_blocks.1.blocks.2.mlp.fc1.bias h_encoder.encoder_blocks.1.blocks.2.mlp.fc2.weight
+        h_encoder.encoder_blocks.1.blocks.2.mlp.fc2.bias h_encoder.encoder_blocks.1.blocks.2.attn.qkv.weight
+        h_encoder.encoder_blocks.1.blocks.2.attn.proj.weight h_encoder.encoder_blocks.1.blocks.2.attn.proj.bias
+        h_encoder.encoder_blocks.1.blocks.3.norm1.weight h_encoder.encoder_blocks.1.blocks.3.norm1.bias
+        h_encoder.encoder_blocks.1.blocks.3.norm2.weight h_encoder.encoder_blocks.1.blocks.3.norm2.bias
+        h_encoder.encoder_blocks.1.blocks.3.mlp.fc1.weight h_encoder.encoder_blocks.1.blocks.3.mlp.fc1.bias
+        h_encoder.encoder_blocks.1.blocks.3.mlp.fc2.weight h_encoder.encoder_blocks.1.blocks.3.mlp.fc2.bias
+        h_encoder.encoder_blocks.1.blocks.3.attn.qkv.weight h_encoder.encoder_blocks.1.blocks.3.attn.proj.weight
+        h_encoder.encoder_blocks.1.blocks.3.attn.proj.bias h_encoder.encoder_blocks.1.blocks.4.norm1.weight
+        h_encoder.encoder_blocks.1.blocks.4.norm1.bias h_encoder.encoder_blocks.1.blocks.4.norm2.weight
+        h_encoder.encoder_blocks.1.blocks.4.norm2.bias h_encoder.encoder_blocks.1.blocks.4.mlp.fc1.weight
+        h_encoder.encoder_blocks.1.blocks.4.mlp.fc1.bias h_encoder.encoder_blocks.1.blocks.4.mlp.fc2.weight
+        h_encoder.encoder_blocks.1.blocks.4.mlp.fc2.bias h_encoder.encoder_blocks.1.blocks.4.attn.qkv.weight
+        h_encoder.encoder_blocks.1.blocks.4.attn.proj.weight h_encoder.encoder_blocks.1.blocks.4.attn.proj.bias
+        h_encoder.encoder_blocks.2.blocks.0.norm1.weight h_encoder.encoder_blocks.2.blocks.0.norm1.bias
+        h_encoder.encoder_blocks.2.blocks.0.norm2.weight h_encoder.encoder_blocks.2.blocks.0.norm2.bias
+        h_encoder.encoder_blocks.2.blocks.0.mlp.fc1.weight h_encoder.encoder_blocks.2.blocks.0.mlp.fc1.bias
+        h_encoder.encoder_blocks.2.blocks.0.mlp.fc2.weight h_encoder.encoder_blocks.2.blocks.0.mlp.fc2.bias
+        h_encoder.encoder_blocks.2.blocks.0.attn.qkv.weight h_encoder.encoder_blocks.2.blocks.0.attn.proj.weight
+        h_encoder.encoder_blocks.2.blocks.0.attn.proj.bias h_encoder.encoder_blocks.2.blocks.1.norm1.weight
+        h_encoder.encoder_blocks.2.blocks.1.norm1.bias h_encoder.encoder_blocks.2.blocks.1.norm2.weight
+        h_encoder.encoder_blocks.2.blocks.1.norm2.bias h_encoder.encoder_blocks.2.blocks.1.mlp.fc1.weight
+        h_encoder.encoder_blocks.2.blocks.1.mlp.fc1.bias h_encoder.encoder_blocks.2.blocks.1.mlp.fc2.weight
+        h_encoder.encoder_blocks.2.blocks.1.mlp.fc2.bias h_encoder.encoder_blocks.2.blocks.1.attn.qkv.weight
+        h_encoder.encoder_blocks.2.blocks.1.attn.proj.weight h_encoder.encoder_blocks.2.blocks.1.attn.proj.bias
+        h_encoder.encoder_blocks.2.blocks.2.norm1.weight h_encoder.encoder_blocks.2.blocks.2.norm1.bias
+        h_encoder.encoder_blocks.2.blocks.2.norm2.weight h_encoder.encoder_blocks.2.blocks.2.norm2.bias
+        h_encoder.encoder_blocks.2.blocks.2.mlp.fc1.weight h_encoder.encoder_blocks.2.blocks.2.mlp.fc1.bias
+        h_encoder.encoder_blocks.2.blocks.2.mlp.fc2.weight h_encoder.encoder_blocks.2.blocks.2.mlp.fc2.bias
+        h_encoder.encoder_blocks.2.blocks.2.attn.qkv.weight h_encoder.encoder_blocks.2.blocks.2.attn.proj.weight
+        h_encoder.encoder_blocks.2.blocks.2.attn.proj.bias h_encoder.encoder_blocks.2.blocks.3.norm1.weight
+        h_encoder.encoder_blocks.2.blocks.3.norm1.bias h_encoder.encoder_blocks.2.blocks.3.norm2.weight
+        h_encoder.encoder_blocks.2.blocks.3.norm2.bias h_encoder.encoder_blocks.2.blocks.3.mlp.fc1.weight
+        h_encoder.encoder_blocks.2.blocks.3.mlp.fc1.bias h_encoder.encoder_blocks.2.blocks.3.mlp.fc2.weight
+        h_encoder.encoder_blocks.2.blocks.3.mlp.fc2.bias h_encoder.encoder_blocks.2.blocks.3.attn.qkv.weight
+        h_encoder.encoder_blocks.2.blocks.3.attn.proj.weight h_encoder.encoder_blocks.2.blocks.3.attn.proj.bias
+        h_encoder.encoder_blocks.2.blocks.4.norm1.weight h_encoder.encoder_blocks.2.blocks.4.norm1.bias
+        h_encoder.encoder_blocks.2.blocks.4.norm2.weight h_encoder.encoder_blocks.2.blocks.4.norm2.bias
+        h_encoder.encoder_blocks.2.blocks.4.mlp.fc1.weight h_encoder.encoder_blocks.2.blocks.4.mlp.fc1.bias
+        h_encoder.encoder_blocks.2.blocks.4.mlp.fc2.weight h_encoder.encoder_blocks.2.blocks.4.mlp.fc2.bias
+        h_encoder.encoder_blocks.2.blocks.4.attn.qkv.weight h_encoder.encoder_blocks.2.blocks.4.attn.proj.weight
+        h_encoder.encoder_blocks.2.blocks.4.attn.proj.bias h_encoder.encoder_norms.0.weight
+        h_encoder.encoder_norms.0.bias h_encoder.encoder_norms.1.weight h_encoder.encoder_norms.1.bias
+        h_encoder.encoder_norms.2.weight h_encoder.encoder_norms.2.bias
+        """,
+}
+
+
+@pytest.mark.parametrize('name', list(FEATURE_MODELS))
+def test_feature_guard_texts_and_state_dict_keys(name):
+    """The guard in front of every feature extractor's trunk: the exact texts of the CPU-tensor error and of the
+    training-mode refusal (DGCNN_feat has none: it answers a CPU tensor in training mode as in evaluation mode), and the
+    state_dict keys, in order."""
+    from point_dae_amd.config import cfg_from_yaml_file
+    from point_dae_amd.registry import MODELS
+    from point_dae_amd import builder  # noqa: F401
+    path, tail = FEATURE_MODELS[name]
+    model = MODELS.build(cfg_from_yaml_file(os.path.join(ROOT, path)).model)
+    assert list(model.state_dict().keys()) == FEATURE_KEYS[name].split()
+    pts = torch.rand(2, 64, 3)
+    cpu = name + ': points must be on the GPU (there is no CPU path)'
+    with pytest.raises(RuntimeError) as err:
+        model.eval()(pts)
+    assert type(err.value) is RuntimeError and str(err.value) == cpu
+    with pytest.raises(RuntimeError if tail is None else NotImplementedError) as err:
+        model.train()(pts)
+    assert str(err.value) == (cpu if tail is None else name + ': evaluation mode only -- ' + tail)
+    assert type(err.value) is (RuntimeError if tail is None else NotImplementedError)
+
+
 def test_the_encoder_switch_is_off_by_default_and_on_in_the_feature_model(monkeypatch):
     """(v) only PointNetv2_feat turns the fused evaluation path on; PDAE_SA_EVAL takes hip or layers."""
     from point_dae_amd import sa_eval_ops
