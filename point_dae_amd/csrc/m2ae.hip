@@ -376,8 +376,9 @@ extern "C" int pdae_m2ae_pack(int B, int G, int Tp, int C, const int32_t* ids, c
                               const float* centres, float* x, float* cen, pdae_stream_t stream) {
   if (int rc = pack_args("m2ae_pack: B >= 0, 0 < T_pad <= G, C a positive multiple of 4 required", B, G, Tp, C)) return rc;
   if (B == 0) return PDAE_OK;
-  if (!ids || !len || !tokens || !centres || !x || !cen) return bad_arg("m2ae_pack: null pointer");
   const long long total = (long long)B * Tp * (C / 4);
+  if ((total + 255) / 256 > 0x7fffffffLL) return unsupported("m2ae_pack: too many elements");
+  if (!ids || !len || !tokens || !centres || !x || !cen) return bad_arg("m2ae_pack: null pointer");
   hipLaunchKernelGGL(m2ae_pack_kernel, dim3(blocks256(total)), dim3(256), 0, as_stream(stream), total, G, Tp, C / 4, ids,
                      len, reinterpret_cast<const float4*>(tokens), centres, reinterpret_cast<float4*>(x), cen);
   return check_launch("m2ae_pack");
@@ -387,8 +388,9 @@ extern "C" int pdae_m2ae_unpack(int B, int G, int Tp, int C, const int32_t* ids,
                                 float* tokens, pdae_stream_t stream) {
   if (int rc = pack_args("m2ae_unpack: B >= 0, 0 < T_pad <= G, C a positive multiple of 4 required", B, G, Tp, C)) return rc;
   if (B == 0) return PDAE_OK;
-  if (!ids || !len || !tokens || !x) return bad_arg("m2ae_unpack: null pointer");
   const long long total = (long long)B * Tp * (C / 4);
+  if ((total + 255) / 256 > 0x7fffffffLL) return unsupported("m2ae_unpack: too many elements");
+  if (!ids || !len || !tokens || !x) return bad_arg("m2ae_unpack: null pointer");
   hipLaunchKernelGGL(m2ae_unpack_kernel, dim3(blocks256(total)), dim3(256), 0, as_stream(stream), total, G, Tp, C / 4, ids,
                      len, reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(tokens));
   return check_launch("m2ae_unpack");
