@@ -1356,6 +1356,36 @@ int pdae_partseg_tail(int S, int N, int K, int P, const float* y, const float* s
                       const int32_t* hi /*nullable*/, float* logp, int32_t* pred, int32_t* shape_iu /*with seg*/,
                       int32_t* shape_correct, int32_t* part_seen, int32_t* part_correct, pdae_stream_t stream);
 
+/* The DGCNN part-segmentation head (segmentation/models/dgcnn_partseg.py:124-140), the same file:
+ *   partseg_cloud_bias_lrelu y (B*N, C) <- lrelu(y + gbias[b]) in place (z > 0 ? z : slope z), gbias (B, C); C a multiple of 4.
+ *   partseg_logits_tail      y (S*N, 128) -> logits (S*N, 50) fp32 = lrelu(y scale + shift) W^T (+ bias, nullable), RAW (no
+ *                            log-softmax); pred = the argmax of the stored logits over [lo[s], hi[s]] as partseg_tail, first
+ *                            index on ties; the counts are partseg_tail's.  K = 128 and P = 50, else PDAE_ERR_UNSUPPORTED
+ *                            before anything is read or launched.  y, scale, shift, W 16-byte aligned. */
+int pdae_partseg_cloud_bias_lrelu(int B, int N, int C, float* y, const float* gbias, float slope, pdae_stream_t stream);
+int pdae_partseg_logits_tail(int S, int N, int K, int P, const float* y, const float* scale, const float* shift, float slope,
+                             const float* W, const float* bias /*nullable*/, const int32_t* seg /*nullable*/,
+                             const int32_t* lo /*nullable*/, const int32_t* hi /*nullable*/, float* logits, int32_t* pred,
+                             int32_t* shape_iu /*with seg*/, int32_t* shape_correct, int32_t* part_seen,
+                             int32_t* part_correct, pdae_stream_t stream);
+
+/* A TWO-layer EdgeConv in EVALUATION mode, forward only, as one kernel (csrc/edge2_eval.hip; the first two EdgeConvs of
+ * segmentation/models/dgcnn_util.py:140-193 dgcnn_encoder_partseg, every BatchNorm2d as its running-estimate affine):
+ *   out[r][c] = max over j of lrelu(scale2[c] (W2[c,:] . h[r][j][:]) + shift2[c])
+ *   h[r][j][:] = lrelu(scale1 (p[b n + idx[r][j]] + q[r]) + shift1),   slope 0.2
+ * pq (b n, 2 C1) = [p | q] = x [W1; W2 - W1]^T, the first layer applied once per point by the caller (edge_weight_stack +
+ * the row GEMM); idx (b, n, k) int32 ids within the cloud (one outside it is clamped, not followed); W2 (C2, C1).  The per-edge
+ * activation h exists only in LDS; the product runs on fp32-input MFMA tiles (one fp32 fma chain per output in the fixed order
+ * k = 0, 4, 1, 5, 2, 6, 3, 7 within every eight); the max starts
+ * from the first edge, j ascending, no atomics.  out (b n, C2); out2 (nullable, row stride ld2 >= C2): a second copy into a
+ * wider row-major tensor, as bn_lrelu_rows.  edge2_eval_supported: 1 for 1 <= k <= 32 and C1 = C2 = 64, else 0;
+ * edge2_eval_forward returns PDAE_ERR_UNSUPPORTED for every other layout before anything is read or launched.
+ * pq, scale1, shift1, W2 16-byte aligned. */
+int pdae_edge2_eval_supported(int k, int C1, int C2);
+int pdae_edge2_eval_forward(int b, int n, int k, int C1, int C2, const float* pq, const int32_t* idx, const float* scale1,
+                            const float* shift1, const float* W2, const float* scale2, const float* shift2, float* out,
+                            float* out2 /*nullable*/, int ld2, pdae_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Measurement aids: box calibration for bench.py (csrc/calib.hip). They replace nothing of the reference; the training
  * step never calls them.  MI355X boxes differ by +-4 % on the step and by up to 12 % on matrix loops (the clock a device

@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from . import dgcnn_cls, point_cae_dgcnn, point_cae_pointnetv2, point_cae_transformer, part_seg, point_m2ae, point_transformer  # noqa: F401  (register the models)
+from . import dgcnn_cls, dgcnn_partseg, point_cae_dgcnn, point_cae_pointnetv2, point_cae_transformer, part_seg, point_m2ae, point_transformer  # noqa: F401  (register the models)
 from .registry import build_model_from_cfg
 
 

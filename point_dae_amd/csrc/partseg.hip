@@ -290,3 +290,155 @@ extern "C" int pdae_partseg_tail(int S, int N, int K, int P, const float* y, con
                      part_seen, part_correct);
   return check_launch("partseg_tail");
 }
+
+// ---- the DGCNN part-segmentation head (segmentation/models/dgcnn_partseg.py:124-140) -----------------------------------
+//   partseg_cloud_bias_lrelu   y[b, n, :] = lrelu(y[b, n, :] + gbias[b, :]) in place: conv8's 1088 per-cloud columns
+//                              [global feature | label feature] as a per-cloud bias behind the 192 per-point columns
+//   partseg_logits_tail        one pass over the 128-wide output of conv10 per point: bn10's affine + LeakyReLU, the
+//                              50 x 128 conv11 (as partseg_tail: W in LDS read as wave-wide broadcasts, the activation
+//                              through a padded LDS tile in chunks of 16 channels, 50 accumulators per lane, k ascending,
+//                              fused multiply-adds), the RAW logits (the DGCNN returns no log-softmax), the argmax of the
+//                              stored logits over the shape's part range and partseg_tail's counts.
+namespace pdae {
+namespace {
+
+constexpr int LT_K = 128;        // the logits tail's input width
+
+// total = B * N * C / 4 quads; grid-stride
+__global__ __launch_bounds__(256) void partseg_cloud_bias_lrelu_kernel(long long total, int N, int C, float slope,
+                                                                       float* __restrict__ y,
+                                                                       const float* __restrict__ gbias) {
+  const int Q = C / 4;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long row = i / Q;
+    const int c = (int)(i % Q) * 4, b = (int)(row / N);
+    float4 v = *reinterpret_cast<float4*>(y + row * C + c);
+    const float4 g = *reinterpret_cast<const float4*>(gbias + (size_t)b * C + c);
+    v.x += g.x, v.y += g.y, v.z += g.z, v.w += g.w;
+    v.x = v.x > 0.f ? v.x : slope * v.x, v.y = v.y > 0.f ? v.y : slope * v.y;
+    v.z = v.z > 0.f ? v.z : slope * v.z, v.w = v.w > 0.f ? v.w : slope * v.w;
+    *reinterpret_cast<float4*>(y + row * C + c) = v;
+  }
+}
+
+// grid (ceil(N / 128), S), block 128: a block's points belong to ONE shape
+__global__ __launch_bounds__(TL_ROWS) void partseg_logits_tail_kernel(
+    int N, const float* __restrict__ y, const float* __restrict__ sc, const float* __restrict__ sh, float slope,
+    const float* __restrict__ W, const float* __restrict__ bias, const int* __restrict__ seg, const int* __restrict__ lo_,
+    const int* __restrict__ hi_, float* __restrict__ logits, int* __restrict__ pred, int* __restrict__ shape_iu,
+    int* __restrict__ shape_correct, int* __restrict__ part_seen, int* __restrict__ part_correct) {
+  __shared__ float Wsm[TL_P * LT_K];
+  __shared__ float Hs[TL_ROWS * (TL_KC + 1)];
+  __shared__ int cnt[4 * TL_P + 1];            // intersection, union, seen, correct per label; the shape's correct points
+  const int s = blockIdx.y, n0 = blockIdx.x * TL_ROWS, tid = threadIdx.x;
+  const int rows = min(TL_ROWS, N - n0);
+  for (int i = tid; i < TL_P * LT_K / 4; i += TL_ROWS)
+    reinterpret_cast<float4*>(Wsm)[i] = reinterpret_cast<const float4*>(W)[i];
+  for (int i = tid; i < 4 * TL_P + 1; i += TL_ROWS) cnt[i] = 0;
+
+  float acc[TL_P];
+#pragma unroll
+  for (int c = 0; c < TL_P; ++c) acc[c] = bias ? bias[c] : 0.f;
+  const size_t base = (size_t)s * N + n0;
+  for (int kc = 0; kc < LT_K; kc += TL_KC) {
+    __syncthreads();                             // the previous chunk has been read (first pass: Wsm and cnt are written)
+#pragma unroll
+    for (int j = 0; j < TL_KC / 4; ++j) {
+      const int i = tid + TL_ROWS * j, row = i / (TL_KC / 4), q = (i % (TL_KC / 4)) * 4;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (row < rows) {
+        v = *reinterpret_cast<const float4*>(y + (base + row) * LT_K + kc + q);
+        const float4 a = *reinterpret_cast<const float4*>(sc + kc + q), d = *reinterpret_cast<const float4*>(sh + kc + q);
+        v.x = v.x * a.x + d.x, v.y = v.y * a.y + d.y, v.z = v.z * a.z + d.z, v.w = v.w * a.w + d.w;
+        v.x = v.x > 0.f ? v.x : slope * v.x, v.y = v.y > 0.f ? v.y : slope * v.y;
+        v.z = v.z > 0.f ? v.z : slope * v.z, v.w = v.w > 0.f ? v.w : slope * v.w;
+      }
+      float* h = Hs + row * (TL_KC + 1) + q;
+      h[0] = v.x, h[1] = v.y, h[2] = v.z, h[3] = v.w;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k4 = 0; k4 < TL_KC; k4 += 4) {
+      const float* h = Hs + tid * (TL_KC + 1) + k4;
+      const float a0 = h[0], a1 = h[1], a2 = h[2], a3 = h[3];
+#pragma unroll
+      for (int c = 0; c < TL_P; ++c) {
+        const float4 w = *reinterpret_cast<const float4*>(Wsm + c * LT_K + kc + k4);      // one address per wave: a broadcast
+        acc[c] = __builtin_fmaf(a3, w.w, __builtin_fmaf(a2, w.z, __builtin_fmaf(a1, w.y, __builtin_fmaf(a0, w.x, acc[c]))));
+      }
+    }
+  }
+
+  if (tid < rows) {
+    const size_t r = base + tid;
+    int lo = lo_ ? lo_[s] : 0, hi = hi_ ? hi_[s] : TL_P - 1;
+    lo = min(max(lo, 0), TL_P - 1), hi = min(hi, TL_P - 1);
+    float best = -INFINITY;
+    int arg = lo;
+#pragma unroll
+    for (int c = 0; c < TL_P; ++c) {
+      logits[r * TL_P + c] = acc[c];
+      if (c >= lo && c <= hi && acc[c] > best) best = acc[c], arg = c;
+    }
+    pred[r] = arg;
+    if (seg) {
+      const int g = seg[r];
+      const bool known = g >= 0 && g < TL_P;
+      atomicAdd(&cnt[TL_P + arg], 1);                                    // union: the predicted label
+      if (g == arg) {
+        atomicAdd(&cnt[arg], 1);
+        atomicAdd(&cnt[3 * TL_P + arg], 1);
+        atomicAdd(&cnt[4 * TL_P], 1);
+      } else if (known && g >= lo && g <= hi) {
+        atomicAdd(&cnt[TL_P + g], 1);                                    // union: the true label, inside the shape's range
+      }
+      if (known) atomicAdd(&cnt[2 * TL_P + g], 1);
+    }
+  }
+  if (!seg) return;                                                      // (uniform over the launch)
+  __syncthreads();
+  if (tid < TL_P) {
+    if (cnt[tid]) atomicAdd(shape_iu + ((size_t)s * 2) * TL_P + tid, cnt[tid]);
+    if (cnt[TL_P + tid]) atomicAdd(shape_iu + ((size_t)s * 2 + 1) * TL_P + tid, cnt[TL_P + tid]);
+    if (cnt[2 * TL_P + tid]) atomicAdd(part_seen + tid, cnt[2 * TL_P + tid]);
+    if (cnt[3 * TL_P + tid]) atomicAdd(part_correct + tid, cnt[3 * TL_P + tid]);
+  }
+  if (tid == 0 && cnt[4 * TL_P]) atomicAdd(shape_correct + s, cnt[4 * TL_P]);
+}
+
+}  // namespace
+}  // namespace pdae
+
+extern "C" int pdae_partseg_cloud_bias_lrelu(int B, int N, int C, float* y, const float* gbias, float slope,
+                                             pdae_stream_t stream) {
+  if (B < 0 || N <= 0 || C <= 0) return bad_arg("partseg_cloud_bias_lrelu: bad size");
+  if (C % 4 != 0) return unsupported("partseg_cloud_bias_lrelu: a width that is a multiple of 4 required");
+  if (B == 0) return PDAE_OK;
+  if (!y || !gbias) return bad_arg("partseg_cloud_bias_lrelu: null pointer");
+  if (((uintptr_t)y | (uintptr_t)gbias) & 15) return bad_arg("partseg_cloud_bias_lrelu: y and gbias must be 16-byte aligned");
+  const long long total = (long long)B * N * (C / 4);
+  const long long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(partseg_cloud_bias_lrelu_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
+                     as_stream(stream), total, N, C, slope, y, gbias);
+  return check_launch("partseg_cloud_bias_lrelu");
+}
+
+extern "C" int pdae_partseg_logits_tail(int S, int N, int K, int P, const float* y, const float* scale, const float* shift,
+                                        float slope, const float* W, const float* bias, const int32_t* seg,
+                                        const int32_t* lo, const int32_t* hi, float* logits, int32_t* pred,
+                                        int32_t* shape_iu, int32_t* shape_correct, int32_t* part_seen,
+                                        int32_t* part_correct, pdae_stream_t stream) {
+  if (S < 0 || N <= 0 || K <= 0 || P <= 0) return bad_arg("partseg_logits_tail: bad size");
+  if (K != LT_K || P != TL_P) return unsupported("partseg_logits_tail: a 128-wide input and 50 part labels required");
+  if ((long long)S * N >= (1LL << 31) / LT_K || S > 65535) return unsupported("partseg_logits_tail: too many points");
+  if (S == 0) return PDAE_OK;
+  if (!y || !scale || !shift || !W || !logits || !pred) return bad_arg("partseg_logits_tail: null pointer");
+  if (seg && (!shape_iu || !shape_correct || !part_seen || !part_correct))
+    return bad_arg("partseg_logits_tail: the counts go with seg");
+  if (((uintptr_t)y | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)W) & 15)
+    return bad_arg("partseg_logits_tail: y, scale, shift and W must be 16-byte aligned");
+  hipLaunchKernelGGL(partseg_logits_tail_kernel, dim3((unsigned)((N + TL_ROWS - 1) / TL_ROWS), (unsigned)S), dim3(TL_ROWS), 0,
+                     as_stream(stream), N, y, scale, shift, slope, W, bias, seg, lo, hi, logits, pred, shape_iu,
+                     shape_correct, part_seen, part_correct);
+  return check_launch("partseg_logits_tail");
+}

@@ -4,7 +4,8 @@ classification fine-tuning runner (--so3_rotation: its rotation-robustness proto
 evaluation of the frozen encoder; --task_affinity: the linear probe whose test loss ranks corruptions; --vote: a ten-vote
 validation behind a high plain one; --way/--shot/--fold: one fold of few-shot fine-tuning), or with --test --ckpts the
 evaluation of a fine-tuned checkpoint: the plain accuracy, then --vote_rounds rounds of ten-vote evaluation; or with
---part_seg --test --ckpts the part-segmentation evaluation of a segmentation checkpoint on ShapeNetPart; or with
+--part_seg --test --ckpts the part-segmentation evaluation of a segmentation checkpoint on ShapeNetPart (the Transformer or,
+with cfgs/segmentation_shapenetpart_dgcnn.yaml, the DGCNN); or with
 --vis_saliency --ckpts its saliency maps: the gradient of the score with respect to every input point of the test set."""
 import torch
 

@@ -24,8 +24,8 @@ vis_saliency_map (:751-833, main.py --vis_saliency) differentiates a fine-tuned 
 input points over the test set, a batch at a time (saliency_ops), and saves the reference's (n, npoints, 6) tensor.
 
 part_seg_test (segmentation/main.py:231-298, main.py --part_seg --test) evaluates a segmentation checkpoint on ShapeNetPart:
-one evaluation pass of part_seg.PointTransformerPartSeg, the metric's integer counts on the device (partseg_ops), one
-read-back, the reference's mIoU lines.
+one evaluation pass of part_seg.PointTransformerPartSeg or dgcnn_partseg.DGCNNPartSeg (the config's model), the metric's
+integer counts on the device (partseg_ops), one read-back, the reference's mIoU lines.
 
 Few-shot fine-tuning (main.py --way/--shot/--fold, datasets.ModelNetFewShot) is run_net on one resident episode: the
 train loader yields the draws of a batch (items, a fresh point shuffle per row) and fewshot_train_points makes the step's
@@ -320,7 +320,8 @@ def test_net(args, config, log=print):
 def part_seg_test(args, config, log=print):
     """segmentation/main.py:231-298 of the reference (main.py --part_seg --test): one pass over the `test` split of
     ShapeNetPart with a segmentation checkpoint (model.load_segmentation_checkpoint(args.ckpts); --scratch_model in
-    place of --ckpts: the initial weights) in evaluation mode.  Every shape's prediction is the argmax over its own
+    place of --ckpts: the initial weights) in evaluation mode; the model is the config's, PointTransformerPartSeg or
+    DGCNNPartSeg (a model may name its own default backend: partseg_mode).  Every shape's prediction is the argmax over its own
     part range, taken from its first point's label; the metric's integer counts stay on the device
     (partseg_ops.Counts) and are read ONCE behind the last batch; the host forms accuracy, class_avg_accuracy, the
     per-category mIoU, class_avg_iou and inctance_avg_iou in float64 and prints the reference's lines.  -> the
@@ -340,7 +341,7 @@ def part_seg_test(args, config, log=print):
     else:
         raise ValueError('ckpts shouldnt be None while test mode')
     base_model = base_model.to(device).eval()
-    log('Part-segmentation backend: %s' % partseg_ops.mode())
+    log('Part-segmentation backend: %s' % getattr(base_model, 'partseg_mode', partseg_ops.mode)())
     counts = partseg_ops.Counts(test_loader.count, device)
     for _, _, (points, cls, seg) in test_loader:
         base_model(points, cls, seg=seg, counts=counts)
